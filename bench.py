@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the path-tracing hot path.
 
-  python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5|C1] [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5|C1] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 A "step" = one crh_render_tiles pass over the rank's tiles of the workload (default BASELINE.json config C3: 1 M random
 triangles, glass + glossy double-layer BSDFs, HDR sky, 1080p; `--spp` samples per pixel per step, default 512 = two batches
 of 1024 tiles x 512 samples: the library cuts a call into batches of <= 2^29 paths).  Inputs are resident in HBM before the timed region.
 
-N = 1, default workload: after the headline leg the OTHER single-GPU configs of BASELINE.json -- C5 (10 M triangles at 4K: the one whose scene does
+A plain run does what the headline figure needs and nothing else: scene set-up, W warm-up steps, EXACTLY K timed steps, the outputs
+(--dump-outputs) and the JSON line (`value` in Mrays/s, `ms_per_step`).  Everything else below -- the other configs, counting pass and roofline,
+counter passes, parity gates, interactive figures, CPU baseline -- runs with --full only.
+
+--dump-outputs DIR: after the timed region, what the timed path computed -- the HDR image the timed steps accumulated (rank 0; at N > 1 the
+assembled frame of the last step) and its ray / sample counts -- as DIR/<name>.npy (float32 / float64, <= 64 MB; a larger image is written as a
+fixed, seeded pixel sample).  The workload is generated from fixed seeds: two builds given the same arguments can be compared output for output.
+
+N = 1, default workload, --full: after the headline leg the OTHER single-GPU configs of BASELINE.json -- C5 (10 M triangles at 4K: the one whose scene does
 not fit the caches, i.e. where HBM is the roof), C2, C1 -- run as short legs (1 warm-up + 4 timed steps) in the same process, each with its own parity
 gates and roofline: config.other_configs_timed.  `value` stays the headline config.  (--other-configs none switches them off.)
 
@@ -125,7 +133,7 @@ def _live_traffic(config, timeout_s, shutil, subprocess, tempfile):
     sys.path.insert(0, os.path.join(ROOT, "profiles"))
     import pmc_fold
     t0 = time.time()
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-interactive", "--no-parity",
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-interactive", "--no-parity",
              "--other-configs", "none", "--live-traffic", "off"]
     vals, launches, tmp = {}, {}, tempfile.mkdtemp(prefix="crh_pmc_")
     env = dict(os.environ, TMPDIR=tmp)
@@ -146,7 +154,7 @@ def _live_traffic(config, timeout_s, shutil, subprocess, tempfile):
     return {"fetch_size_kb_per_launch": vals["FETCH_SIZE"], "write_size_kb_per_launch": vals["WRITE_SIZE"],
             "hbm_bytes_per_launch": vals["FETCH_SIZE"] * 1024 * 2 + vals["WRITE_SIZE"] * 1024, "launches_per_pass": launches["FETCH_SIZE"],
             "seconds": round(time.time() - t0, 1),
-            "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes, each with --kernel-trace only) around `bench.py --config %s --steps 2 --warmup 1 --no-cpu "
+            "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes, each with --kernel-trace only) around `bench.py --full --config %s --steps 2 --warmup 1 --no-cpu "
                    "--no-interactive --no-parity --other-configs none`, started by THIS run as child processes after its timed region; per launch of the timed traversal "
                    "instantiations (k_trace_packets + fall-back pass, k_trace_nearest<false, ...>); bytes = FETCH_SIZE*1024*2 + WRITE_SIZE*1024 (gfx950 x2 read-side "
                    "correction); memory-side counter, Infinity-Cache hits included" % config}
@@ -385,6 +393,11 @@ def parse_args(argv=None):
     ap.add_argument("--allow-unchecked", action="store_true",
                     help="exit 0 even when NO parity gate of the headline leg produced a verdict (checker could not run); default: exit code 3 (a failed gate: 1)")
     ap.add_argument("--no-shared-build", action="store_true", help="N > 1: every rank builds its own BVH (default: rank 0 builds, the others take its tree)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what the timed path computed (HDR image of the timed steps, ray / sample counts) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline figure: other configs, counting pass + roofline, counter passes, parity gates, interactive "
+                         "figures, CPU baseline (default: off -- set-up, warm-up, the timed steps and the JSON line only)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -394,14 +407,16 @@ def parse_args(argv=None):
         args.steps = 1 if args.config == "C4" else 4
     if args.other_configs is None:
         plain = args.gpus == 1 and args.config == "C3" and not (args.tris or args.width or args.height or args.spp)
-        args.other_configs = "C5,C2,C1,CAD1M" if plain else "none"
+        args.other_configs = "C5,C2,C1,CAD1M" if plain and args.full else "none"
     if args.live_traffic is None:
         plain = args.gpus == 1 and args.config == "C3" and not (args.tris or args.width or args.height or args.spp) and args.other_configs != "none"
-        args.live_traffic = "on" if plain else "off"
+        args.live_traffic = "on" if plain and args.full else "off"
     args.other_list = [c for c in args.other_configs.split(",") if c and c != "none"]
     for c in args.other_list:
         if c not in ("C1", "C2", "C3", "C5", "CAD1M"):
             ap.error(f"--other-configs: unknown config {c}")
+    if not args.full and (args.other_list or args.live_traffic == "on"):
+        ap.error("--other-configs / --live-traffic on measure beyond the headline figure: add --full")
     return args
 
 
@@ -465,6 +480,9 @@ def main():
 
     ctxt = {"world": world, "rank": rank, "local": local, "dist": dist, "backend": backend, "torch": torch}
     out, failed, errors = run_leg(args, ctxt, args.config, args.steps, args.warmup, args.spp, headline=True)
+    outputs = out.pop("_outputs", None) if out is not None else None
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
 
     # ---- the other single-GPU configs of BASELINE.json, driver-timed in the same run (verdict r3 item 1): short legs, own parity gates, own roofline.
     # `value` stays the headline config; C5 (10 M triangles, 4K) is the one whose scene does not fit the caches, i.e. where HBM is the roof.
@@ -488,9 +506,9 @@ def main():
     if rank == 0:
         if errors:
             out["checker_errors"] = errors
-        # a headline number no gate looked at is not a measurement (a parity gate accompanies every number)
+        # a headline number no gate looked at is not a measurement (a parity gate accompanies every number) -- the gates are part of --full
         verdicts = [p for p in (out.get("parity"), out.get("parity_step0")) if p is not None and "error" not in p]
-        unchecked = not args.no_parity and not verdicts
+        unchecked = args.full and not args.no_parity and not verdicts
         flatten_line(out)
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -503,6 +521,28 @@ def main():
     if unchecked and not args.allow_unchecked:
         print("bench.py: NO parity gate of the headline leg produced a verdict -- the number is unchecked (exit 3; --allow-unchecked accepts it)", file=sys.stderr)
         sys.exit(3)
+
+
+OUTPUT_BYTES_MAX = 64 << 20          # --dump-outputs: all files of one run together
+OUTPUT_SAMPLE_SEED = 20240917
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32 / float64.  An image too large for the budget (C5's 4K frame: 99.5 MB) is written as a
+    fixed, seeded sample of its pixels, <name>_sample.npy, beside the flat pixel indices of that sample, <name>_sample_pixels.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.ndim < 3)
+    for name, a in arrays.items():
+        if a.ndim == 3 and a.nbytes + small > OUTPUT_BYTES_MAX - (1 << 20):
+            h, w, c = a.shape
+            k = min(h * w, (OUTPUT_BYTES_MAX // 2) // (c * 4 + 8))
+            pix = np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(h * w, size=k, replace=False))
+            np.save(os.path.join(d, f"{name}_sample.npy"), a.reshape(h * w, c)[pix])
+            np.save(os.path.join(d, f"{name}_sample_pixels.npy"), pix.astype(np.float64))
+        else:
+            np.save(os.path.join(d, f"{name}.npy"), a)
 
 
 def flatten_line(out):
@@ -688,7 +728,7 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
         step(i)
     barrier()
     v.reset()
-    v.enable_kernel_timing(True)
+    v.enable_kernel_timing(True)                              # on in every run: the timed steps are the same launches with or without --full
     t_render[0] = t_assemble[0] = 0.0
     barrier()
     t0 = time.perf_counter()
@@ -697,12 +737,16 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
     barrier()
     dt = time.perf_counter() - t0
     v.enable_kernel_timing(False)
-    kt = v.kernel_timing()
+    full = args.full
     st = v.stats()
-    pk = v.packet_stats()                                     # camera rays of the timed steps walked as packets / handed to the per-ray fall-back pass
-    # what the TIMED steps themselves accumulated (rank 0, N = 1): the parity gate below compares exactly these pixels with the oracle
-    timed_hdr = v.read_hdr() if (rank == 0 and world == 1 and not args.no_parity) else None
-    if rank == 0 and world > 1 and not args.no_parity and assembled[0] is not None:
+    if full:
+        kt = v.kernel_timing()
+        pk = v.packet_stats()                                 # camera rays of the timed steps walked as packets / handed to the per-ray fall-back pass
+    gates = full and not args.no_parity
+    dump = headline and rank == 0 and args.dump_outputs is not None
+    # what the TIMED steps themselves accumulated (rank 0, N = 1): the parity gate below compares exactly these pixels with the oracle, --dump-outputs writes them
+    timed_hdr = v.read_hdr() if (rank == 0 and world == 1 and (gates or dump)) else None
+    if rank == 0 and world > 1 and (gates or dump) and assembled[0] is not None:
         # N > 1: the frame the LAST timed step's exchange assembled on rank 0 (every rank's tiles, the same samples) goes through the same gate
         timed_hdr = assembled[0][..., :3].contiguous().cpu().numpy()
     timed_first, timed_n = warmup * spp_step, steps * spp_step
@@ -726,7 +770,7 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
     # ---- counting pass (untimed): the same frames again with node / triangle counters on (rank 0's shard)
     roof = None
     wide_batch = (spp_step * len(tiles) * sc.params.tile_size ** 2) > (12 << 20) and (spp_step & -spp_step) >= 64      # crh_context.h: packets from 64 consecutive samples per pixel on
-    if rank == 0:
+    if rank == 0 and full:
         v.reset(); v.enable_counters(True)
         for i in range(steps):
             v.render_tiles(tiles, (warmup + i) * spp_step, spp_step)
@@ -761,16 +805,16 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
     # ---- first-timed-step replay (verdict r3 item 4a): the samples of the FIRST timed step again, untimed, same schedule (one wide batch), counters off;
     # the oracle checks >= 32 tiles of it whatever --steps is -- the whole-region gate below covers fewer tiles the more samples the timed region holds
     step0_hdr = None
-    if rank == 0 and world == 1 and not args.no_parity:
+    if rank == 0 and world == 1 and gates:
         v.reset()
         v.render_tiles(tiles, warmup * spp_step, spp_step)
         step0_hdr = v.read_hdr()
 
     # ---- the reference's interactive regime (one Redraw() = +1 spp per call, AppViewer.cxx:1045-1047), reported beside `value`
     interactive = None
-    if headline and rank == 0 and world == 1 and not args.no_interactive:
+    if full and headline and rank == 0 and world == 1 and not args.no_interactive:
         interactive = interactive_figures(v, sc.camera)
-    elif rank == 0 and world == 1 and not args.no_interactive:
+    elif full and rank == 0 and world == 1 and not args.no_interactive:
         # the other legs: the lone frame after a restart only (crh_reset + crh_render(1) + crh_sync, median of 9) -- what a user of THIS scene waits for
         import statistics
         for _ in range(96):                                   # the library's own measurements for this scene come first (crh_get_frame_tuning: <= 30 frames; crh_get_tile_order: ~ 16 more)
@@ -794,7 +838,7 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
     failed = False
     wide = (spp_step * len(tiles) * sc.params.tile_size ** 2) > (12 << 20)
     sched = ("big-batch (wide), counters off" if wide else "small-batch, counters off")
-    if rank == 0 and (timed_hdr is not None or step0_hdr is not None):
+    if rank == 0 and gates and (timed_hdr is not None or step0_hdr is not None):
         try:
             gate = ParityOracle(sc)
             if timed_hdr is not None:
@@ -854,7 +898,7 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
 
     # ---- CPU baseline: the oracle (a port, not the reference: OCCT has no CPU path tracer) on this box's cores
     cpu = None
-    if headline and rank == 0 and not args.no_cpu and world == 1:          # reported on rank 0 at N = 1 only
+    if full and headline and rank == 0 and not args.no_cpu and world == 1:          # reported on rank 0 at N = 1 only
         try:
             cpu = cpu_baseline(sc, args.cpu_seconds)
         except Exception as e:
@@ -885,6 +929,9 @@ def run_leg(args, ctxt, config, steps, warmup, spp_arg, headline):
             "dtype": "f32", "data": "synthetic", "config": cfgd,
             "roofline": roof, "cpu_baseline": cpu, "parity": parity, "parity_step0": parity0,
         }
+        cfgd["full"] = full
+        if dump and timed_hdr is not None:
+            out["_outputs"] = {"hdr": timed_hdr, "ray_counts": np.array([rays_n, rays_a, samples], np.float64)}
     return out, failed, errors
 
 

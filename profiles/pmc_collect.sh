@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for cfg in $CFGS; do
-  ARGS="--config $cfg --steps 2 --warmup 1 --no-cpu --no-interactive --no-parity --other-configs none"
+  ARGS="--full --config $cfg --steps 2 --warmup 1 --no-cpu --no-interactive --no-parity --other-configs none"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$cfg/trace -o t -- python3 $REPO/bench.py $ARGS > $OUT/$cfg.trace.log 2>&1
   grep '^{"metric"' $OUT/$cfg.trace.log | tail -1 > $OUT/$cfg.bench.json
   # memory side (FETCH_SIZE costs 3 of the 4 TCC slots, WRITE_SIZE 2: separate passes), L2 hit / miss, L2-side requests, and one SQ pass

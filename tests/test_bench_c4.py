@@ -24,7 +24,7 @@ def _bench(args, timeout):
 
 @pytest.mark.gpu
 def test_c4_as_written_on_one_gpu(hip_lib):
-    out = _bench(["--config", "C4", "--spp", "4096", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive", "--parity-seconds", "4", "--step0-seconds", "4"], 1500)
+    out = _bench(["--full", "--config", "C4", "--spp", "4096", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive", "--parity-seconds", "4", "--step0-seconds", "4"], 1500)
     assert out["scaling"] == "strong" and out["n_gpus"] == 1 and out["value"] > 500
     assert out["config"]["workload"].startswith("C4: 1000000") and out["config"]["spp_per_step_per_rank"] == 4096
     assert out["parity"]["bit_exact"] is True and out["parity"]["spp"] == 4096 and out["parity"]["pixels"] > 0
@@ -34,7 +34,7 @@ def test_c4_as_written_on_one_gpu(hip_lib):
 
 @pytest.mark.gpu
 def test_c5_wide_batch_on_the_10m_triangle_tree(hip_lib):
-    out = _bench(["--config", "C5", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive"], 1500)
+    out = _bench(["--full", "--config", "C5", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive"], 1500)
     assert out["config"]["workload"].startswith("C5: 10000000") and out["config"]["spp_per_step_per_rank"] == 256
     assert "3840x2160" in out["config"]["workload"] and out["value"] > 500
     assert out["parity"]["bit_exact"] is True and "wide" in out["parity"]["schedule"] and out["parity"]["pixels"] > 0

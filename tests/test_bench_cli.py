@@ -63,10 +63,12 @@ def test_strong_and_weak_defaults():
     a = bench.parse_args(["--config", "C4"])
     assert a.scaling == "strong" and a.steps == 1 and a.other_list == []
     a = bench.parse_args([])
-    assert a.scaling == "weak" and a.config == "C3" and a.gpus == 1
-    assert a.other_list == ["C5", "C2", "C1", "CAD1M"]             # the default single-GPU run also times the other configs (config.other_configs_timed)
-    assert bench.parse_args(["--gpus", "8"]).other_list == [] and bench.parse_args(["--config", "C2"]).other_list == []
-    assert bench.parse_args(["--other-configs", "none"]).other_list == [] and bench.parse_args(["--steps", "20", "--warmup", "5"]).other_list == ["C5", "C2", "C1", "CAD1M"]
+    assert a.scaling == "weak" and a.config == "C3" and a.gpus == 1 and not a.full
+    assert a.other_list == [] and a.live_traffic == "off"            # a plain run measures the headline only
+    a = bench.parse_args(["--full"])
+    assert a.other_list == ["C5", "C2", "C1", "CAD1M"]             # the default single-GPU --full run also times the other configs (config.other_configs_timed)
+    assert bench.parse_args(["--full", "--gpus", "8"]).other_list == [] and bench.parse_args(["--full", "--config", "C2"]).other_list == []
+    assert bench.parse_args(["--full", "--other-configs", "none"]).other_list == [] and bench.parse_args(["--full", "--steps", "20", "--warmup", "5"]).other_list == ["C5", "C2", "C1", "CAD1M"]
 
 
 def test_a_broken_checker_is_not_a_failed_gate(monkeypatch):
@@ -138,8 +140,9 @@ def test_counter_passes_of_this_run_replace_the_committed_bytes(tmp_path, monkey
     r = bench.roofline_report("C3", 128, False, 1.4e11, 16.0, 81 << 20, {}, live=live)
     assert r["traffic"] == live["hbm_bytes_per_launch"] and r["frac"] is not None and r["committed_passes"].startswith("stale") and "ceilings" not in r
     # the default: on for the plain headline run only; never inside a profiled process
-    assert bench.parse_args([]).live_traffic == "on" and bench.parse_args(["--other-configs", "none"]).live_traffic == "off"
-    assert bench.parse_args(["--config", "C5"]).live_traffic == "off" and bench.parse_args(["--gpus", "2"]).live_traffic == "off"
+    assert bench.parse_args(["--full"]).live_traffic == "on" and bench.parse_args(["--full", "--other-configs", "none"]).live_traffic == "off"
+    assert bench.parse_args(["--full", "--config", "C5"]).live_traffic == "off" and bench.parse_args(["--full", "--gpus", "2"]).live_traffic == "off"
+    assert bench.parse_args([]).live_traffic == "off"
     monkeypatch.setenv("ROCPROFILER_SOMETHING", "1")
     assert bench.being_profiled() and "profiler" in bench.live_traffic("C3")["error"]
 
@@ -197,7 +200,7 @@ def test_committed_counter_traffic_belongs_to_this_build():
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_report_two(hip_lib):
     """the whole N = 2 flow (spawn, tile shards, framebuffer reduce, rank-0 report) on the single GPU of the test box"""
-    p, out = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu", "--config", "C1", "--spp", "4"],
+    p, out = _run(["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu", "--config", "C1", "--spp", "4"],
                   {"CRH_BENCH_SHARE_DEVICE": "1", "CRH_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert out["n_gpus"] == 2 and out["config"]["rccl_ranks"] == 2 and out["value"] > 0
@@ -219,7 +222,7 @@ def test_two_ranks_on_one_gpu_report_two(hip_lib):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["reduce", "gather"])
 def test_both_exchange_steps_pass_the_gate(hip_lib, mode):
-    p, out = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu", "--config", "C1", "--spp", "4", "--assemble", mode],
+    p, out = _run(["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu", "--config", "C1", "--spp", "4", "--assemble", mode],
                   {"CRH_BENCH_SHARE_DEVICE": "1", "CRH_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert out["config"]["assemble"]["mode"] == mode and out["parity"]["bit_exact"] and out["parity"]["pixels"] > 0
@@ -232,7 +235,7 @@ def test_c3_at_the_weak_scaling_step_size_of_two_ranks(hip_lib, mode):
     spp x N = 1024 samples of its Morton-interleaved half of the tiles in ONE crh_render_tiles call (wide batches of 1020 tiles) -- on the one GPU of the test
     box, both exchange steps; the assembled frame goes through the oracle gates.  No curve is measured here (two ranks share a device): the point is that the
     first real SCALE run cannot fail on something a rehearsal would have caught."""
-    p, out = _run(["--gpus", "2", "--config", "C3", "--steps", "2", "--warmup", "1", "--no-cpu", "--assemble", mode], {"CRH_BENCH_SHARE_DEVICE": "1", "CRH_BENCH_BACKEND": "gloo"}, timeout=1500)
+    p, out = _run(["--full", "--gpus", "2", "--config", "C3", "--steps", "2", "--warmup", "1", "--no-cpu", "--assemble", mode], {"CRH_BENCH_SHARE_DEVICE": "1", "CRH_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     cfg = out["config"]
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and cfg["workload"].startswith("C3: 1000000")
@@ -250,7 +253,7 @@ def test_c3_at_the_weak_scaling_step_size_of_two_ranks(hip_lib, mode):
 def test_other_configs_are_timed_in_the_same_run(hip_lib):
     """verdict r3 item 1: the default run times further single-GPU configs after the headline, each with its own gates and roofline; here with the
     small ones so that the test stays short (C5's own leg: tests/test_bench_c4.py)"""
-    p, out = _run(["--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive", "--config", "C2", "--other-configs", "C1", "--other-steps", "2"], {}, timeout=900)
+    p, out = _run(["--full", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-interactive", "--config", "C2", "--other-configs", "C1", "--other-steps", "2"], {}, timeout=900)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert out["config"]["workload"].startswith("C2") and out["parity_step0"]["tiles"] >= 32 and out["parity_step0"]["bit_exact"]
     o = out["config"]["other_configs_timed"]["C1"]
@@ -268,3 +271,68 @@ def test_strong_scaling_step_is_the_fixed_job(hip_lib):
     assert p1.returncode == 0 and p2.returncode == 0, (p1.stderr + p2.stderr)[-3000:]
     assert o1["scaling"] == o2["scaling"] == "strong"
     assert o1["config"]["rays_nearest"] == o2["config"]["rays_nearest"]         # same job, sharded: same rays in total
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """a plain run is set-up, warm-up, the timed steps and the line: what measures or checks beyond the headline figure is asked for with --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    for extra in (["--other-configs", "C1"], ["--live-traffic", "on"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(extra)
+        a = bench.parse_args(["--full"] + extra)
+        assert a.full and (a.other_list == ["C1"] or a.live_traffic == "on")
+    a = bench.parse_args(["--steps", "7", "--warmup", "2", "--dump-outputs", "d"])
+    assert a.steps == 7 and a.warmup == 2 and a.dump_outputs == "d" and not a.full
+
+
+def test_dumped_outputs_stay_within_their_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, at most 64 MB together; an image too large for that (C5's 4K frame) becomes the same seeded pixel
+    sample in every run"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    small = np.arange(64 * 48 * 3, dtype=np.float32).reshape(48, 64, 3)
+    bench.write_outputs(str(tmp_path / "s"), {"hdr": small, "ray_counts": np.array([1.0, 2.0, 3.0])})
+    assert np.array_equal(np.load(tmp_path / "s" / "hdr.npy"), small)
+    assert np.load(tmp_path / "s" / "ray_counts.npy").dtype == np.float64
+    big = np.random.default_rng(5).random((2160, 3840, 3), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"hdr": big, "ray_counts": np.zeros(3)})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["hdr_sample.npy", "hdr_sample_pixels.npy", "ray_counts.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.OUTPUT_BYTES_MAX
+    pix = np.load(tmp_path / "a" / "hdr_sample_pixels.npy")
+    got = np.load(tmp_path / "a" / "hdr_sample.npy")
+    assert pix.dtype == np.float64 and got.dtype == np.float32 and len(pix) == len(got) > 10 ** 6
+    assert np.array_equal(got, big.reshape(-1, 3)[pix.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_the_timed_steps_computed(hip_lib, oracle_lib, tmp_path):
+    """a plain run: exactly --steps timed steps, no legs beyond the headline, and --dump-outputs writes the image the timed steps accumulated -- the
+    same bits in a second run, and the oracle's for the same samples"""
+    import numpy as np
+    args = ["--config", "C1", "--spp", "8", "--steps", "3", "--warmup", "1"]
+    p, out = _run(args + ["--dump-outputs", str(tmp_path / "a")], {})
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0 and out["metric"] == "Mrays/s"
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None and out["config"]["interactive"] is None
+    assert "other_configs_timed" not in out["config"] and out["config"]["full"] is False
+    hdr = np.load(tmp_path / "a" / "hdr.npy")
+    counts = np.load(tmp_path / "a" / "ray_counts.npy")
+    assert hdr.shape == (512, 512, 3) and hdr.dtype == np.float32 and np.isfinite(hdr).all() and hdr.mean() > 0
+    assert counts.tolist() == [out["config"]["rays_nearest"], out["config"]["rays_any"], 512 * 512 * 8 * 3]
+    p, _ = _run(args + ["--dump-outputs", str(tmp_path / "b")], {})
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    assert np.array_equal(np.load(tmp_path / "b" / "hdr.npy").view(np.uint32), hdr.view(np.uint32))
+    from cadrays_amd import scenes
+    o = oracle_lib.Oracle().load_scene(scenes.baseline_config("C1"))
+    tiles = np.arange(0, o.n_tiles(), 7, dtype=np.uint32)
+    o.render_tiles(tiles, 8, 24)                                   # samples [8, 32): the three timed steps after one warm-up step of 8
+    ref = o.read_accum()
+    o.close()
+    mask = ref[..., 3] == 24
+    assert mask.sum() > 0 and np.array_equal(hdr[mask].view(np.uint32), np.ascontiguousarray(ref[..., :3][mask], np.float32).view(np.uint32))
