@@ -1576,7 +1576,8 @@ ORC_API int orc_bsdf_sample(const crh_bsdf* m, const float wo[3], float weight_i
   *flags_out = (delta ? 1 : 0) | (inside ? 2 : 0);
   return alive;
 }
-/* elementary functions, vectorised over n, for checking crh_math.h against libm in the tests */
+/* elementary functions, vectorised over n, for checking crh_math.h against libm in the tests; the codes are those of the
+ * product's k_debug_math (cadrays_amd/csrc/k_accumulate.h), so one test drives both sides */
 ORC_API void orc_math(int fn, const float* a, const float* b, float* out, float* out2, uint32_t n)
 {
   for (uint32_t i = 0; i < n; ++i) switch (fn) {
@@ -1587,15 +1588,24 @@ ORC_API void orc_math(int fn, const float* a, const float* b, float* out, float*
     case 4: out[i] = crh_acos(a[i]); break;
     case 5: out[i] = crh_atan2(a[i], b[i]); break;
     case 6: crh_sincos(a[i], &out[i], &out2[i]); break;
+    case 7: out[i] = crh_sqrt(a[i]); break;
+    case 8: out[i] = a[i] / b[i]; break;
+    case 9: { uint32_t s = crh_rng_seed(crh_f2u(a[i]), crh_f2u(b[i])); out[i] = crh_rng_next(&s); out2[i] = crh_rng_next(&s); } break;
+    case 10: { const v3 x = crh_norm3(crh_mk3(a[i], b[i], a[i] * b[i])); out[i] = x.x; out2[i] = crh_dot3(x, crh_mk3(b[i], a[i], 1.0f)); } break;
     default: out[i] = 0.f;
   }
 }
 ORC_API void orc_rng_stream(uint32_t pixel, uint32_t fseed, float* out, uint32_t n)
 { uint32_t s = crh_rng_seed(pixel, fseed); for (uint32_t i = 0; i < n; ++i) out[i] = crh_rng_next(&s); }
 ORC_API uint32_t orc_frame_seed(uint32_t seed, uint32_t n) { return frame_seed(seed, n); }
-/* the uniform drawn from xorshift state `s_after` under either setting of crh_spec.uniform_32bit (the conversion crh_rng_next_mode applies) */
 /* test hooks for the split-scene pre-test (include/crh_math.h): the padded sphere around a box, and "does [0, tmax] of the ray come within it" */
 ORC_API void orc_box_sphere(const float* lo, const float* hi, float* s4) { crh_box_sphere(lo, hi, s4); }
 ORC_API int orc_ray_near_sphere(const float* o, const float* d, float tmax, const float* s4)
 { return crh_ray_near_sphere(crh_mk3(o[0], o[1], o[2]), crh_mk3(d[0], d[1], d[2]), tmax, s4[0], s4[1], s4[2], s4[3]); }
+/* the same two, vectorised over n: boxes lo[3i..], hi[3i..] -> s4[4i..]; rays o[3i..], d[3i..], tmax[i] against s4[4i..] -> near[i] */
+ORC_API void orc_box_spheres(const float* lo, const float* hi, float* s4, uint32_t n)
+{ for (uint32_t i = 0; i < n; ++i) crh_box_sphere(lo + 3 * (size_t)i, hi + 3 * (size_t)i, s4 + 4 * (size_t)i); }
+ORC_API void orc_rays_near_sphere(const float* o, const float* d, const float* tmax, const float* s4, int32_t* near, uint32_t n)
+{ for (uint32_t i = 0; i < n; ++i) near[i] = orc_ray_near_sphere(o + 3 * (size_t)i, d + 3 * (size_t)i, tmax[i], s4 + 4 * (size_t)i); }
+/* the uniform drawn from xorshift state `s_after` under either setting of crh_spec.uniform_32bit (the conversion crh_rng_next_mode applies) */
 ORC_API float orc_rng_float(uint32_t s_after, int full32) { return full32 ? (float)s_after * 2.3283064365386963e-10f : (float)(s_after >> 8) * 5.9604644775390625e-8f; }

@@ -147,6 +147,27 @@ def math_fn(fn, a, b=None):
     return out, out2
 
 
+def box_spheres(lo, hi):
+    """crh_box_sphere for each box: lo, hi (n, 3) float32 -> (n, 4) {centre, padded radius}"""
+    lo = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+    s4 = np.empty((len(lo), 4), np.float32)
+    lib().orc_box_spheres(lo.ctypes.data_as(_f32p), hi.ctypes.data_as(_f32p), s4.ctypes.data_as(_f32p), C.c_uint32(len(lo)))
+    return s4
+
+
+def rays_near_sphere(o, d, tmax, s4):
+    """crh_ray_near_sphere for each ray: o, d (n, 3), tmax (n,), s4 (n, 4) float32 -> (n,) bool"""
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    tmax = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (len(o),)))
+    s4 = np.ascontiguousarray(np.broadcast_to(np.asarray(s4, np.float32), (len(o), 4)))
+    near = np.empty(len(o), np.int32)
+    lib().orc_rays_near_sphere(o.ctypes.data_as(_f32p), d.ctypes.data_as(_f32p), tmax.ctypes.data_as(_f32p), s4.ctypes.data_as(_f32p),
+                               near.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint32(len(o)))
+    return near != 0
+
+
 def rng_stream(pixel, fseed, n):
     out = np.empty(n, np.float32)
     lib().orc_rng_stream(C.c_uint32(pixel), C.c_uint32(fseed), out.ctypes.data_as(_f32p), C.c_uint32(n))
