@@ -55,6 +55,16 @@ class crh_spec(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class crh_pick_result(C.Structure):
+    """what crh_pick reports for one pixel (include/cadrays_hip.h)"""
+    _fields_ = [("object", C.c_int32), ("triangle", C.c_int32), ("t", C.c_float), ("depth", C.c_float), ("u", C.c_float), ("v", C.c_float),
+                ("point", C.c_float * 3)]
+
+    def as_dict(self):
+        return {"object": int(self.object), "triangle": int(self.triangle), "t": self.t, "depth": self.depth, "u": self.u, "v": self.v,
+                "point": tuple(self.point)}
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -73,4 +83,5 @@ EXPORTS = [
     "crh_save_accum", "crh_load_accum", "crh_accum_device_ptr", "crh_reduce", "crh_enable_counters", "crh_get_stats", "crh_trace_nearest",
     "crh_trace_any", "crh_get_bvh", "crh_get_tlas", "crh_build_bvh_host", "crh_bench_trace", "crh_debug_math", "crh_debug_bsdf", "crh_enable_kernel_timing",
     "crh_get_kernel_timing", "crh_get_packet_stats", "crh_debug_reduce_fake_devices", "crh_get_path_budget", "crh_get_frame_tuning", "crh_get_tile_order", "crh_build_prebuilt", "crh_query_pipeline_capacity", "crh_env_table",
+    "crh_camera_rays", "crh_pick", "crh_read_ids", "crh_set_selection", "crh_set_hover", "crh_get_selection_bounds",
 ]

@@ -304,6 +304,47 @@ class Backend:
         self._call("get_stats", C.byref(s))
         return s.as_dict()
 
+    # -- picking, hover, selection (crh_pick.cpp) ------------------------------------------
+    def camera_rays(self, xy):
+        """crh_camera_rays: the pixel-centre primary rays of the (x, y) pixels, (n, 8) float32 in trace_nearest's layout"""
+        xy = np.ascontiguousarray(xy, np.uint32).reshape(-1, 2)
+        out = np.empty((len(xy), 8), np.float32)
+        self._call("camera_rays", xy.ctypes.data_as(_u32p), C.c_uint32(len(xy)), _fp(out))
+        return out
+
+    def pick(self, x, y):
+        """crh_pick == MoveTo + PickedData: dict(object, triangle, t, depth, u, v, point) under pixel (x, y); object -1 = nothing"""
+        r = abi.crh_pick_result()
+        self._call("pick", C.c_uint32(int(x)), C.c_uint32(int(y)), C.byref(r))
+        return r.as_dict()
+
+    def read_ids(self):
+        """crh_read_ids: (object int32, triangle int32, t float32), each (H, W)"""
+        ob, tr = np.empty((self.height, self.width), np.int32), np.empty((self.height, self.width), np.int32)
+        t = np.empty((self.height, self.width), np.float32)
+        self._call("read_ids", ob.ctypes.data_as(_i32p), tr.ctypes.data_as(_i32p), _fp(t))
+        return ob, tr, t
+
+    def set_selection(self, selected, rgb=(255, 160, 0), alpha=64):
+        """crh_set_selection: one flag per object (None = nothing selected), outline colour, interior alpha 0..255; only read_ldr shows it"""
+        if selected is None:
+            self._call("set_selection", None, C.c_uint32(0), None, C.c_uint32(0))
+            return
+        f = np.ascontiguousarray(np.asarray(selected) != 0, np.uint8)
+        col = (C.c_uint8 * 3)(*[int(v) for v in rgb])
+        self._call("set_selection", f.ctypes.data_as(_u8p), C.c_uint32(len(f)), col, C.c_uint32(int(alpha)))
+
+    def set_hover(self, obj, rgb=(0, 255, 255), alpha=32):
+        """crh_set_hover: the object under the cursor (-1 / None = none)"""
+        col = (C.c_uint8 * 3)(*[int(v) for v in rgb])
+        self._call("set_hover", C.c_int32(-1 if obj is None else int(obj)), col, C.c_uint32(int(alpha)))
+
+    def selection_bounds(self):
+        """crh_get_selection_bounds: (lo, hi) world-space box of the selected objects under the current transforms"""
+        lo, hi = np.empty(3, np.float32), np.empty(3, np.float32)
+        self._call("get_selection_bounds", _fp(lo), _fp(hi))
+        return lo, hi
+
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)

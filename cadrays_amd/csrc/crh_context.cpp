@@ -140,6 +140,7 @@ int do_reset(crh_ctx* c)
   CRH_HIP(hipMemsetAsync(c->d_accum, 0, sizeof(float4) * (size_t)c->par.width * c->par.height, cs));
   CRH_HIP(hipMemsetAsync(c->d_m2, 0, sizeof(float) * (size_t)c->par.width * c->par.height, cs));
   c->adaptive_picks = 0; c->pending_n = 0; c->ramp_k = 1; c->picked_valid = false; c->assembled_valid = false;
+  c->ids_valid = false;                                  // whatever restarts the accumulation may have changed what lies under a pixel (crh_pick.cpp)
   {   // per-tile costs of the accumulation that ends here: to the host (pinned, asynchronous, behind the frames in flight), then zero for the next one
     crh_ctx::TileOrder& to = c->tile_order;
     // a host that restarts while frames are still running is dragging: it gets no new list (replacing the list waits for the frames that read it -- measured:
@@ -299,6 +300,7 @@ void crh_destroy(crh_ctx* c)
   if (c->rb_fork) hipEventDestroy(c->rb_fork);
   for (void* q : {(void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) hipFree(q);
   release_comms(c);
+  release_pick(c);
   hipStreamDestroy(c->stream_);
   delete c;
 }

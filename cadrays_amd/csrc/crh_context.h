@@ -5,6 +5,7 @@
 //   crh_schedule.cpp   the wavefront schedule: lanes, batches, frame pipelining, look-ahead, adaptive iterations; crh_render / crh_render_tiles
 //   crh_readback.cpp   HDR / LDR read-back (synchronous and asynchronous), accumulator checkpoints, statistics and kernel timing
 //   crh_reduce.cpp     crh_reduce (RCCL over xGMI, or peer copies on one device)
+//   crh_pick.cpp       the first-hit id buffer: camera rays, pick, id read-back, selection / hover state and bounds, the overlay of the LDR read-out
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
@@ -210,6 +211,22 @@ struct ReadbackState {
   uint32_t rb_head = 0, rb_outstanding = 0; bool rb_guard_pending = false; hipEvent_t rb_guard = nullptr;
 };
 
+// ---- the first-hit id buffer (crh_pick.cpp): DERIVED state -- object / triangle / distance under every pixel centre for the camera, target size, geometry, transforms,
+// visibility flags and tree in force.  do_reset and crh_set_camera clear ids_valid; the buffer is computed on the first pick / id read-back / overlaid LDR read-out after
+// that, on a stream of its own (crh_render never launches it), kept on the device, and a further crh_pick is one 16-byte copy.  Selection and hover are plain host
+// state; only the LDR read-out looks at them.
+struct PickState {
+  hipStream_t pk_stream = nullptr; hipEvent_t pk_fork = nullptr;
+  float4* d_pk_rays = nullptr; float4* d_pk_hit_slot = nullptr; size_t pk_cap_slots = 0;     // per ray slot (8x8-block order): the ray, what the traversal kernel answered
+  float4* d_pk_hit = nullptr; int32_t* d_pk_obj = nullptr; size_t pk_cap_px = 0;             // per pixel, row-major: {t, u, v, caller's triangle index}, object
+  int32_t* d_pk_tri_obj = nullptr; size_t pk_tri_obj_cap = 0; bool pk_tri_obj_dirty = true;  // c->tri_obj on the device (uploaded on first need after crh_build / crh_add_object)
+  uint32_t* d_pk_cursor = nullptr; DCounters* d_pk_counters = nullptr;                       // work cursor and counter block of the id pass (crh_stats never sees its rays)
+  bool ids_valid = false; uint32_t ids_w = 0, ids_h = 0;
+  std::vector<uint8_t> sel; bool sel_any = false; uint8_t sel_rgb[3] = {0, 0, 0}; uint32_t sel_alpha = 0;
+  uint8_t* d_sel = nullptr; size_t sel_cap = 0; bool sel_dirty = false;
+  int32_t hover = -1; uint8_t hov_rgb[3] = {0, 0, 0}; uint32_t hov_alpha = 0;
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -220,7 +237,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -307,6 +324,11 @@ int upload_textures(crh_ctx* c);
 
 // ---- crh_schedule.cpp
 uint32_t frame_seed(uint32_t seed, uint32_t n);
+
+// ---- crh_pick.cpp
+int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // hover / selection over the tone-mapped bytes at d_ldr, enqueued on `on`; nothing at all when neither is set
+void clear_selection(crh_ctx* c);
+void release_pick(crh_ctx* c);
 
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);

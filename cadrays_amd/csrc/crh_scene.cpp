@@ -267,6 +267,7 @@ int crh_set_geometry(crh_ctx* c, const float* pos, const float* nrm, const float
   if (uv) c->uv.assign(uv, uv + 2 * (size_t)nV); else c->uv.clear();
   c->tri.assign(tri, tri + 4 * (size_t)nT);
   c->two_level = false; c->nO = 0; c->xf.clear(); c->tri_obj.clear(); c->hidden.clear();      // a new scene: everything displayed
+  clear_selection(c); c->ids_valid = false; c->pk_tri_obj_dirty = true;                       // ... nothing selected or hovered
   if (tri_obj && xf && nO) {
     // two-level mode: vertices stay in object space; every object gets its own tree (crh_build), the top-level tree
     // over the instances carries the transforms (crh_set_transforms rebuilds only that)
@@ -454,7 +455,7 @@ int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* 
   TwoLevelState::Obj o{}; o.first = T0; o.ntri = nT; o.static0 = false; o.in_static = false;
   c->objs.push_back(o);
   if (!c->hidden.empty()) c->hidden.push_back(0);
-  c->nO = ob + 1;
+  c->nO = ob + 1; c->pk_tri_obj_dirty = true;
   if (object_out) *object_out = ob;
   return apply_objects(c, nullptr, nullptr);
 }
@@ -530,6 +531,7 @@ int crh_set_camera(crh_ctx* c, const crh_camera* cam)
                      cam->fovy_deg, cam->aspect, cam->ortho_scale, cam->aperture_radius, cam->focal_dist};
   if (!all_finite(f, sizeof f / sizeof f[0], 1.0e30f)) return fail(c, CRH_E_INVALID, "camera holds a NaN / Inf");
   c->cam = *cam; c->pending_n = 0;                      // samples traced ahead with the old camera are dropped
+  c->ids_valid = false;                                 // ... and so is the first-hit id buffer (crh_pick.cpp)
   c->read_since_render = true;
   return CRH_OK;
 }
@@ -738,6 +740,7 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
   }
   if (c->two_level && !c->hidden.empty()) { if (c->hidden.size() != c->nO) c->hidden.assign(c->nO, 0); if ((rc = apply_objects(c, nullptr, nullptr))) return rc; }      // objects erased before the build: baked like the rest, then disabled
   rc = do_reset(c); if (rc) return rc;
+  c->pk_tri_obj_dirty = true;                            // the triangle-to-object table of the id buffer follows the scene (crh_pick.cpp uploads it on first need)
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
 }

@@ -54,6 +54,13 @@ void launch_scatter_tris(const Launch&, float4* tris, const uint32_t* pos, const
 // API-level ray tracing on a plain ray buffer (8 floats per ray)
 void launch_trace_rays(const Launch&, const DScene&, const float4* rays, uint32_t n, int any_hit,
                        float4* out_hit, uint32_t* out_vis, uint32_t* d_cursor, DCounters*);
+// The first-hit id buffer (k_ids.h): pixel-centre camera rays of the whole target in 8x8-block order (d_xy == nullptr, n = 64 x blocks) or of a pixel list; the rays
+// are traced with launch_trace_rays; resolve = row-major {t, u, v, triangle} + object per pixel.  launch_overlay: hover / selection over tone-mapped bytes.
+void launch_first_hit_rays(const Launch&, const DScene&, const uint32_t* d_xy, uint32_t n, float4* rays);
+void launch_first_hit_resolve(const Launch&, uint32_t W, uint32_t H, uint32_t n_slots, const float4* hit_slot, const int32_t* tri_obj, uint32_t n_tri_obj, float4* hit_px, int32_t* obj_px);
+void launch_overlay(const Launch&, uint8_t* ldr, const int32_t* obj_px, uint32_t W, uint32_t H, const uint8_t* sel_flags /* nullptr: no selection */, uint32_t n_flags, const uint8_t sel_rgb[3],
+                    uint32_t sel_alpha, int32_t hover /* -1: none */, const uint8_t hov_rgb[3], uint32_t hov_alpha);
+void pixel_centre_ray_host(const DScene&, uint32_t px, uint32_t py, float o[3], float d[3]);      // the same function on the host (crh_pick's point and depth)
 void launch_debug_math(const Launch&, int fn, const float* a, const float* b, float* out, float* out2, uint32_t n);
 // test hook: eval / pdf / sample / Fresnel of the layered BSDF on caller-supplied local directions (m: 8 x float4 = crh_bsdf)
 void launch_debug_bsdf(const Launch&, int fn, const float4* m, const float* a, const float* b, float* out, uint32_t n, int two_sided);

@@ -29,6 +29,7 @@ namespace {
 #include "k_shade.h"
 #include "k_frame.h"
 #include "k_accumulate.h"
+#include "k_ids.h"
 
 }  // namespace
 
@@ -206,6 +207,28 @@ void launch_trace_rays(const Launch& L, const DScene& S, const float4* rays, uin
   else         { if (L.counters) CRH_LAUNCH_TR2(false, true) else CRH_LAUNCH_TR2(false, false) }
 #undef CRH_LAUNCH_TR2
 #undef CRH_LAUNCH_TR
+}
+// ---- the first-hit id buffer and the hover / selection overlay (k_ids.h)
+void launch_first_hit_rays(const Launch& L, const DScene& S, const uint32_t* d_xy, uint32_t n, float4* rays)
+{
+  if (n) hipLaunchKernelGGL(k_first_hit_rays, dim3(min((uint32_t)L.grid, (n + kBlock - 1u) / kBlock)), dim3(kBlock), 0, L.stream, S, d_xy, n, rays);
+}
+void launch_first_hit_resolve(const Launch& L, uint32_t W, uint32_t H, uint32_t n_slots, const float4* hit_slot, const int32_t* tri_obj, uint32_t n_tri_obj, float4* hit_px, int32_t* obj_px)
+{
+  if (n_slots) hipLaunchKernelGGL(k_first_hit_resolve, dim3(min((uint32_t)L.grid, (n_slots + kBlock - 1u) / kBlock)), dim3(kBlock), 0, L.stream, W, H, n_slots, hit_slot, tri_obj, n_tri_obj, hit_px, obj_px);
+}
+void launch_overlay(const Launch& L, uint8_t* ldr, const int32_t* obj_px, uint32_t W, uint32_t H, const uint8_t* sel_flags, uint32_t n_flags, const uint8_t sel_rgb[3], uint32_t sel_alpha,
+                    int32_t hover, const uint8_t hov_rgb[3], uint32_t hov_alpha)
+{
+  const OverlaySet sel{sel_flags, sel_flags ? n_flags : 0u, -1, sel_rgb[0], sel_rgb[1], sel_rgb[2], sel_alpha};
+  const OverlaySet hov{nullptr, 0u, hover, hov_rgb[0], hov_rgb[1], hov_rgb[2], hov_alpha};
+  hipLaunchKernelGGL(k_overlay, dim3(min((uint32_t)L.grid, (W * H + kBlock - 1u) / kBlock)), dim3(kBlock), 0, L.stream, ldr, obj_px, W, H, sel, hov);
+}
+void pixel_centre_ray_host(const DScene& S, uint32_t px, uint32_t py, float o[3], float d[3])
+{
+  crh_v3 o3, d3;
+  pixel_centre_ray(S, px, py, o3, d3);
+  o[0] = o3.x; o[1] = o3.y; o[2] = o3.z; d[0] = d3.x; d[1] = d3.y; d[2] = d3.z;
 }
 void launch_debug_math(const Launch& L, int fn, const float* a, const float* b, float* out, float* out2, uint32_t n)
 {

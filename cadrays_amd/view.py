@@ -26,6 +26,8 @@ class View(Backend):
         super().__init__(load_library(), "crh_", (C.c_int(int(device)),))
         self.device = int(device)
         self._params = None
+        self._camera, self._n_objects, self._selected, self._visible = None, 1, set(), None
+        self.selection_rgb, self.selection_alpha, self.hover_rgb, self.hover_alpha = (255, 160, 0), 64, (0, 255, 255), 32
         import os
         from . import pipeline_capacity
         frames, _ = pipeline_capacity()
@@ -53,6 +55,73 @@ class View(Backend):
         if self._params is None:
             raise RuntimeError("set_params / load_scene first")
         self.set_params(dataclasses.replace(self._params, **fields))
+
+    # ---- AIS_InteractiveContext vocabulary: hover, selection, autofocus (crh_pick.cpp) ---------------
+    def set_geometry(self, pos, nrm, tri, uv=None, tri_object=None, obj_xform=None):
+        super().set_geometry(pos, nrm, tri, uv, tri_object, obj_xform)
+        self._n_objects = 1 if tri_object is None else len(np.asarray(obj_xform, np.float32).reshape(-1, 12))
+        self._selected, self._visible = set(), None          # a new scene: nothing selected, everything displayed
+
+    def add_object(self, pos, nrm, tri, xform, uv=None):
+        ob = super().add_object(pos, nrm, tri, xform, uv)
+        self._n_objects = ob + 1
+        if self._visible is not None:
+            self._visible = np.append(self._visible, np.uint8(1))
+        return ob
+
+    def set_visibility(self, visible):
+        super().set_visibility(visible)
+        self._visible = np.ascontiguousarray(np.asarray(visible) != 0, np.uint8)
+
+    def set_camera(self, cam):
+        self._camera = dataclasses.replace(cam)
+        super().set_camera(cam)
+
+    def _push_selection(self):
+        flags = np.zeros(self._n_objects, np.uint8)
+        flags[sorted(self._selected)] = 1
+        self.set_selection(flags if self._selected else None, self.selection_rgb, self.selection_alpha)
+
+    def MoveTo(self, x, y):
+        """AIS_InteractiveContext::MoveTo (AppViewer.cxx:347): the object under the cursor becomes the hovered one; returns it (-1: none)"""
+        ob = self.pick(x, y)["object"]
+        self.set_hover(ob, self.hover_rgb, self.hover_alpha)
+        return ob
+
+    def Select(self, x, y, shift=False):
+        """Select / ShiftSelect (AppViewer.cxx:359-455): a click replaces the selection by the object under the cursor (nothing there: clears it),
+        a shift-click toggles that object; returns the selected set"""
+        ob = self.pick(x, y)["object"]
+        if shift:
+            if ob >= 0:
+                self._selected ^= {ob}
+        else:
+            self._selected = {ob} if ob >= 0 else set()
+        self._push_selection()
+        return set(self._selected)
+
+    def HideSelected(self):
+        """"Hide selected" (AppViewer.cxx:1149-1153): erase the selected objects (set_visibility) and drop the selection"""
+        if not self._selected:
+            return
+        if self._n_objects == 1 and not getattr(self, "_has_objects", False):
+            raise RuntimeError("HideSelected needs a scene handed over with objects")
+        vis = np.ones(self._n_objects, np.uint8) if self._visible is None else self._visible.copy()
+        vis[sorted(self._selected)] = 0
+        self._selected = set()
+        self._push_selection()
+        self.set_hover(-1)
+        self.set_visibility(vis)
+
+    def autofocus(self, x, y):
+        """autofocus (AppGui.cxx:78-94): CameraFocalPlaneDist = depth of what lies under the pixel; like every camera change it restarts the
+        accumulation.  Nothing under the pixel: nothing changes.  Returns the new focal distance or None."""
+        r = self.pick(x, y)
+        if r["object"] < 0:
+            return None
+        self.set_camera(dataclasses.replace(self._camera, focal_dist=float(r["depth"])))
+        self.reset()
+        return float(r["depth"])
 
     # ---- device-side extras -----------------------------------------------------------------
     def sync(self):

@@ -330,6 +330,41 @@ CRH_API int crh_reduce(crh_ctx* const* ctxs, uint32_t n, uint32_t root);
 CRH_API int crh_enable_counters(crh_ctx* ctx, int on);
 CRH_API int crh_get_stats(crh_ctx* ctx, crh_stats* out);
 
+/* --- picking, hover and selection (crh_pick.cpp) -------------------------------------------------------------------------------------------------
+ * What the application does to a RENDERED scene on every mouse move and click.  All of it reads one DERIVED buffer, the first-hit id buffer: the object,
+ * triangle and distance the pixel-centre primary ray of every pixel meets first -- the ray of crh_render's camera model (pinhole, orthographic, crh_spec.h #13)
+ * with sub-pixel jitter (0.5, 0.5) and no lens sample, traced by the kernels of crh_trace_nearest over the scene as it is drawn: erased objects are not
+ * pickable, moved objects are picked where they are.  It is computed by the first of these calls after a change of camera, target size, geometry, transform,
+ * visibility or tree (anything that restarts the accumulation, and crh_set_camera), on a stream of its own, and kept on the device; crh_render never
+ * computes it.  NONE of these calls restarts or touches the accumulation: the HDR image and the frame counter are what they would have been without them.
+ * `triangle` is the caller's triangle index -- the row of `tri` in crh_set_geometry, the rows of crh_add_object following -- which is also what
+ * crh_trace_nearest reports as prim (the leaf position is mapped back on the device).  `object` = tri_object[triangle]; -1 on a miss; 0 for every hit of
+ * a scene handed over without objects (such a scene counts as ONE object for crh_set_selection / crh_set_hover). */
+typedef struct { int32_t object, triangle; float t, depth, u, v; float point[3]; } crh_pick_result;
+/* pixel-centre primary rays of the current camera for the n listed pixels (x, y pairs), 8 floats each in crh_trace_nearest's layout
+ * {o.xyz, tmax = 1e15, d.xyz, 0}: feeding them to crh_trace_nearest reproduces the id buffer.  (No counterpart in the reference: OCCT's selector builds
+ * its own pick frustum, SelectMgr_ViewerSelector::Pick behind AppViewer.cxx:347.) */
+CRH_API int crh_camera_rays(crh_ctx* ctx, const uint32_t* xy /* 2n */, uint32_t n, float* rays_out /* 8n */);
+/* == AIS_InteractiveContext::MoveTo + PickedData(1) (AppViewer.cxx:347, AppGui.cxx:78-94): what lies under pixel (x, y).  point = o + t d of the pixel's
+ * ray, u / v = the hit's barycentric coordinates, depth = dot(point - eye, view direction) = what CameraFocalPlaneDist takes for autofocus.  A miss:
+ * object = triangle = -1, t = 1e15, the rest zero.  Served from the valid buffer with one 16-byte copy. */
+CRH_API int crh_pick(crh_ctx* ctx, uint32_t x, uint32_t y, crh_pick_result* out);
+/* the whole buffers, W*H each, row 0 = top; any of the three may be NULL */
+CRH_API int crh_read_ids(crh_ctx* ctx, int32_t* object_out, int32_t* triangle_out, float* t_out);
+/* == the selected / detected sets of AIS_InteractiveContext as drawn (Select / ShiftSelect AppViewer.cxx:359-455, MoveTo :347): flags per object, colour,
+ * interior alpha 0..255.  crh_read_ldr and crh_read_ldr_begin/_end (ONLY those: crh_read_hdr*, crh_save_accum and crh_reduce never see it) draw, after tone
+ * map and after the ShowSamplingTiles outline: a pixel is MARKED for a set when its object is in the set; a marked pixel on the image border or with a
+ * 4-neighbour that is not marked for the same set takes the set's colour (outline); every other marked pixel becomes (ldr * (256 - alpha) + colour * alpha
+ * + 128) >> 8 per channel (alpha 0 = outline only).  The selection first, then the hovered object.  With no selection and no hover the bytes are the tone
+ * map's.  selected == NULL clears the selection.  After crh_add_object the flags take n_objects + 1 entries (flags set before stay); a new crh_set_geometry
+ * clears selection and hover.  Multi-GPU: every context holds the whole scene, hence its own id buffer for the whole image; the overlay is drawn by the
+ * context that serves the LDR read-out. */
+CRH_API int crh_set_selection(crh_ctx* ctx, const uint8_t* selected /* n_objects or NULL = none */, uint32_t n_objects, const uint8_t rgb[3], uint32_t alpha);
+CRH_API int crh_set_hover(crh_ctx* ctx, int32_t object /* -1 = none */, const uint8_t rgb[3], uint32_t alpha);
+/* == the Bnd_Box over SelectedInteractive() that the manipulator takes as its pivot (AppViewer.cxx:863-875): world-space box of the vertices of the selected
+ * objects under the CURRENT transforms (erased objects included while they stay selected).  Nothing selected: CRH_E_INVALID. */
+CRH_API int crh_get_selection_bounds(crh_ctx* ctx, float lo[3], float hi[3]);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
