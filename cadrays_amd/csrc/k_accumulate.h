@@ -195,6 +195,10 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_pick(const float* __restric
 __device__ __forceinline__ float hable(float x)
 {
   const float A = 0.22f, B = 0.30f, Cc = 0.10f, D = 0.20f, E = 0.01f, F = 0.30f;
+  // the curve saturates at A / A - E / F, but from x ~ 3.9e19 on A x^2 overflows and the quotient would be inf / inf = NaN, which the clamp below turns into BLACK
+  // (an unclamped firefly's +inf among them).  Above 2^60 numerator and denominator are the same float (B, CB lie 2^-60 below A x): cutting x there changes no
+  // finite result that did not overflow, and every larger one -- +inf included -- takes the limit
+  x = crh_min(x, 1.152921504606846976e18f);
   return (CRH_FMA(x, CRH_FMA(A, x, Cc * B), D * E) / CRH_FMA(x, CRH_FMA(A, x, B), D * F)) - E / F;
 }
 __global__ __launch_bounds__(kBlock) void k_tonemap(const float4* __restrict__ accum, uint8_t* __restrict__ out, uint32_t n,

@@ -46,6 +46,8 @@
  *                                     lit 0.85 tile over its 0.45 neighbour at       ratio at 1.335
  *                                     1.365 .. 1.382 = (0.85 / 0.45) ^ (1 / gamma)
  *                                     with gamma 1.97 .. 2.04 on every icon
+ *     (not a switch) the display rule before the gamma: NaN / negative -> 0, times 2^exposure, in filmic mode hable(v) / hable(white point) with the curve's
+ *     input cut at 2^60 -- it saturates, so +inf and anything whose square overflows is drawn white, as in linear mode -- then clamp to [0, 1]
  *
  * Reference evidence that these are the knobs that matter: the only numbers CADRays itself pins are the BSDF / light / camera /
  * parameter vectors of its input contract (cadrays_hip.h cites them line by line); everything in the table is arithmetic inside

@@ -1194,6 +1194,8 @@ static int render_tiles(orc_ctx* c, const uint32_t* tiles, uint32_t nt, uint32_t
 static float hable(float x)
 {
   const float A = 0.22f, B = 0.30f, C = 0.10f, D = 0.20f, E = 0.01f, F = 0.30f;
+  /* saturate instead of inf / inf = NaN (drawn black) once A x^2 overflows: above 2^60 numerator and denominator are the same float already (k_accumulate.h hable) */
+  x = crh_min(x, 1.152921504606846976e18f);
   return (CRH_FMA(x, CRH_FMA(A, x, C * B), D * E) / CRH_FMA(x, CRH_FMA(A, x, B), D * F)) - E / F;
 }
 static uint8_t to_ldr(const crh_params* p, int gamma22, float v)
@@ -1485,6 +1487,16 @@ ORC_API int orc_render(orc_ctx* c, uint32_t n)
   return render_tiles(c, NULL, 0, first, n, NULL);
 }
 ORC_API int orc_read_accum(orc_ctx* c, float* out) { if (!c || !c->accum) return CRH_E_INVALID; memcpy(out, c->accum, sizeof(float) * 4 * (size_t)c->par.width * c->par.height); return 0; }
+/* crh_load_accum's contract: the accumulator (rgb mean + sample count) and the iteration counter are replaced as they are;
+ * refused while adaptive sampling is on (a checkpoint does not carry the second moments) */
+ORC_API int orc_load_accum(orc_ctx* c, const float* in, uint32_t frames_done)
+{
+  if (!c || !in || !c->accum) { if (c) snprintf(c->err, sizeof c->err, "no accumulator / null input"); return CRH_E_INVALID; }
+  if (c->adaptive) { snprintf(c->err, sizeof c->err, "checkpoints do not carry the adaptive sampler's second moments"); return CRH_E_INVALID; }
+  memcpy(c->accum, in, sizeof(float) * 4 * (size_t)c->par.width * c->par.height);
+  c->frames_done = frames_done;
+  return 0;
+}
 ORC_API int orc_read_hdr(orc_ctx* c, float* out)
 {
   if (!c || !c->accum) return CRH_E_INVALID;

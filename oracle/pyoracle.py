@@ -64,6 +64,12 @@ class Oracle(Backend):
         self._call("read_accum", out.ctypes.data_as(C.POINTER(C.c_float)))
         return out
 
+    def load_accum(self, rgba, frames_done):
+        """orc_load_accum: the product's way in (View.load_accum), refused while adaptive sampling is on"""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        assert rgba.shape == (self.height, self.width, 4)
+        self._call("load_accum", rgba.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(int(frames_done)))
+
 
 _FAST = None
 
