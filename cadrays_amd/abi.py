@@ -65,10 +65,25 @@ class crh_pick_result(C.Structure):
                 "point": tuple(self.point)}
 
 
+class crh_meter_params(C.Structure):
+    """the metering rule's parameters (include/cadrays_hip.h; crh_meter_defaults fills them: METER_DEFAULTS below)"""
+    _fields_ = [("key_stops", C.c_float), ("min_stops", C.c_float), ("max_stops", C.c_float), ("white_permille", C.c_uint32),
+                ("white_min", C.c_float), ("white_max", C.c_float), ("rect", C.c_uint32 * 4)]
+
+
+class crh_meter_result(C.Structure):
+    """what crh_measure_exposure reports (include/cadrays_hip.h)"""
+    _fields_ = [("hist", C.c_uint32 * 256), ("n_unsampled", C.c_uint32), ("n_lit", C.c_uint32), ("exposure", C.c_float), ("white_point", C.c_float),
+                ("white_bin", C.c_uint32)]
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
 
+METER_DEFAULTS = dict(key_stops=_f32(-2.4739311883324122), min_stops=-10.0, max_stops=10.0, white_permille=990, white_min=1.0, white_max=10.0, rect=(0, 0, 0, 0))      # key: log2(0.18)
+
+assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_bsdf) == 128 and C.sizeof(crh_light) == 32 and C.sizeof(crh_spec) == 52
 
 SCHEDULE_AUTO, SCHEDULE_WIDE, SCHEDULE_SMALL, SCHEDULE_STAGED = 0, 1, 2, 3      # crh_set_schedule
@@ -84,4 +99,5 @@ EXPORTS = [
     "crh_trace_any", "crh_get_bvh", "crh_get_tlas", "crh_build_bvh_host", "crh_bench_trace", "crh_debug_math", "crh_debug_bsdf", "crh_enable_kernel_timing",
     "crh_get_kernel_timing", "crh_get_packet_stats", "crh_debug_reduce_fake_devices", "crh_get_path_budget", "crh_get_frame_tuning", "crh_get_tile_order", "crh_build_prebuilt", "crh_query_pipeline_capacity", "crh_env_table",
     "crh_camera_rays", "crh_pick", "crh_read_ids", "crh_set_selection", "crh_set_hover", "crh_get_selection_bounds",
+    "crh_set_display", "crh_get_display", "crh_meter_defaults", "crh_meter_from_histogram", "crh_set_auto_exposure", "crh_measure_exposure",
 ]

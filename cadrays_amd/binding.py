@@ -37,6 +37,17 @@ def _close_all():
             pass
 
 
+def meter_params(**fields):
+    """abi.crh_meter_params: the defaults (abi.METER_DEFAULTS == crh_meter_defaults) with the named fields replaced; an unknown name is an error"""
+    unknown = sorted(set(fields) - set(abi.METER_DEFAULTS))
+    if unknown:
+        raise ValueError(f"no such metering parameter {unknown}; crh_meter_params has {sorted(abi.METER_DEFAULTS)}")
+    v = dict(abi.METER_DEFAULTS); v.update(fields)
+    p = abi.crh_meter_params(float(v["key_stops"]), float(v["min_stops"]), float(v["max_stops"]), int(v["white_permille"]), float(v["white_min"]), float(v["white_max"]))
+    p.rect[:] = [int(x) for x in v["rect"]]
+    return p
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -298,6 +309,34 @@ class Backend:
         out = np.empty(shape, np.float32)
         self._call("read_hdr_end", _fp(out))
         return out
+
+    # -- display state and auto exposure (no restart; SettingsWidget.cxx:343-404) -----------
+    def set_display(self, tonemap_mode, exposure, white_point):
+        """crh_set_display: tone-map mode, exposure [stops] and white point of every LDR read-out from now on; the accumulation goes on"""
+        self._call("set_display", C.c_int(int(tonemap_mode)), C.c_float(float(exposure)), C.c_float(float(white_point)))
+
+    def get_display(self):
+        """crh_get_display: dict(tonemap_mode, exposure, white_point, auto_on) as in force"""
+        m, e, w, a = C.c_int(0), C.c_float(0), C.c_float(0), C.c_int(0)
+        self._call("get_display", C.byref(m), C.byref(e), C.byref(w), C.byref(a))
+        return {"tonemap_mode": int(m.value), "exposure": e.value, "white_point": w.value, "auto_on": bool(a.value)}
+
+    def set_auto_exposure(self, on=True, **params):
+        """crh_set_auto_exposure: every LDR read-out meters the image it is about to show (fields of crh_meter_params by name, the others take
+        crh_meter_defaults; rect = (x0, y0, x1, y1)); on=False / None switches it off.  The accumulation goes on."""
+        if not on:
+            self._call("set_auto_exposure", None)
+            return
+        p = meter_params(**params)
+        self._call("set_auto_exposure", C.byref(p))
+
+    def measure_exposure(self, **params):
+        """crh_measure_exposure: one synchronous metering of the image read_ldr would show; dict(hist (256,) uint32, n_unsampled, n_lit, exposure,
+        white_point, white_bin).  Changes nothing: hand exposure and white_point to set_display to apply them."""
+        p, r = meter_params(**params), abi.crh_meter_result()
+        self._call("measure_exposure", C.byref(p), C.byref(r))
+        return {"hist": np.frombuffer(r, np.uint32, 256).copy(), "n_unsampled": int(r.n_unsampled), "n_lit": int(r.n_lit),
+                "exposure": np.float32(r.exposure), "white_point": np.float32(r.white_point), "white_bin": int(r.white_bin)}
 
     def stats(self):
         s = abi.crh_stats()

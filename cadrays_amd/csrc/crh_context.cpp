@@ -298,6 +298,7 @@ void crh_destroy(crh_ctx* c)
   if (c->rb_stream) { hipStreamSynchronize(c->rb_stream); hipStreamDestroy(c->rb_stream); }
   for (int k = 0; k < 2; ++k) { if (c->d_rb[k]) hipFree(c->d_rb[k]); if (c->h_rb[k]) hipHostFree(c->h_rb[k]); if (c->rb_tm[k]) hipEventDestroy(c->rb_tm[k]); if (c->rb_done[k]) hipEventDestroy(c->rb_done[k]); }
   if (c->rb_fork) hipEventDestroy(c->rb_fork);
+  if (c->d_meter) hipFree(c->d_meter);
   for (void* q : {(void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) hipFree(q);
   release_comms(c);
   release_pick(c);

@@ -209,6 +209,10 @@ struct ReadbackState {
   hipStream_t rb_stream = nullptr; hipEvent_t rb_fork = nullptr, rb_tm[2] = {nullptr, nullptr}, rb_done[2] = {nullptr, nullptr};
   uint8_t* d_rb[2] = {nullptr, nullptr}; uint8_t* h_rb[2] = {nullptr, nullptr}; size_t rb_cap = 0, rb_bytes[2] = {0, 0}; bool rb_hdr[2] = {false, false};
   uint32_t rb_head = 0, rb_outstanding = 0; bool rb_guard_pending = false; hipEvent_t rb_guard = nullptr;
+  // auto exposure (crh_set_auto_exposure; kernels in k_meter.h): while on, every LDR read-out meters the image in front of its tone map, on the stream it uses anyway.
+  // Four metering blocks (allocated on first need): [0] the synchronous read-out, [1] / [2] the two read-back slots, [3] crh_measure_exposure -- the context's
+  // stream and the read-back stream never share one.  The display values themselves are par.tonemap_mode / exposure / white_point: only the tone map reads them.
+  bool meter_on = false; crh_meter_params meter_par{}; DMeter* d_meter = nullptr;
 };
 
 // ---- the first-hit id buffer (crh_pick.cpp): DERIVED state -- object / triangle / distance under every pixel centre for the camera, target size, geometry, transforms,

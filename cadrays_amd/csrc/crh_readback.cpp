@@ -5,6 +5,40 @@
 using namespace crh;
 using namespace crh::api;
 
+// ---- auto exposure (crh_set_auto_exposure): the metering in front of an LDR read-out's tone map.  Block 0 belongs to the synchronous read-out, 1 / 2 to the two
+// read-back slots, 3 to crh_measure_exposure.
+static bool meter_params_ok(const crh_meter_params* p)
+{
+  const float f[] = {p->key_stops, p->min_stops, p->max_stops, p->white_min, p->white_max};
+  return all_finite(f, sizeof f / sizeof f[0]) && p->min_stops <= p->max_stops && p->white_min <= p->white_max && p->white_permille <= 1000u;
+}
+static MeterRule meter_rule_of(const crh_meter_params& p, float exposure_in, float white_in)
+{
+  return MeterRule{p.key_stops, p.min_stops, p.max_stops, p.white_permille, p.white_min, p.white_max, exposure_in, white_in};
+}
+// memset + k_luma_histogram + k_meter on L.stream over the image the tone map is about to read; the rectangle is cut to the target, an empty one is the whole frame
+static void meter_image(crh_ctx* c, const Launch& L, const float4* src, const crh_meter_params& p, DMeter* block)
+{
+  const uint32_t W = c->par.width, H = c->par.height;
+  uint32_t x0 = std::min(p.rect[0], W), y0 = std::min(p.rect[1], H), x1 = std::min(p.rect[2], W), y1 = std::min(p.rect[3], H);
+  if (x1 <= x0 || y1 <= y0) { x0 = 0; y0 = 0; x1 = W; y1 = H; }
+  launch_meter(L, src, W, x0, y0, x1 - x0, y1 - y0, meter_rule_of(p, c->par.exposure, c->par.white_point), block);
+}
+// what launch_tonemap takes as `metered`: nullptr (auto exposure off: the code path and bytes of a context that never heard of it) or the block just filled
+static const float* meter_in_front(crh_ctx* c, const Launch& L, const float4* src, int block)
+{
+  if (!c->meter_on || !c->d_meter) return nullptr;
+  meter_image(c, L, src, c->meter_par, c->d_meter + block);
+  return c->d_meter[block].metered;
+}
+static int ensure_meter_blocks(crh_ctx* c)
+{
+  if (c->d_meter) return CRH_OK;
+  CRH_HIP(hipSetDevice(c->device));
+  CRH_HIP(hipMalloc((void**)&c->d_meter, 4 * sizeof(DMeter)));
+  return CRH_OK;
+}
+
 extern "C" {
 
 int crh_read_hdr(crh_ctx* c, float* out)
@@ -32,7 +66,8 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   int rc = ensure_scratch(c, 3 * (size_t)n); if (rc) return rc;
   const uint8_t* d_mask = overlay ? c->d_picked : nullptr;            // written by the device-side tile draw of the last iteration
   Launch L{cstream(c), c->grid, false};
-  launch_tonemap(L, c->assembled_valid ? c->d_assembled : c->d_accum, (uint8_t*)c->d_scratch, n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts);
+  const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
+  launch_tonemap(L, src, (uint8_t*)c->d_scratch, n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, meter_in_front(c, L, src, 0));
   if ((rc = overlay_ldr(c, L.stream, (uint8_t*)c->d_scratch))) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
   CRH_HIP(hipMemcpyAsync(out, c->d_scratch, 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
@@ -73,7 +108,7 @@ static int read_begin(crh_ctx* c, bool hdr)
   else {
     const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
     const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked && c->tile_stat_cap >= n_tiles;
-    launch_tonemap(L, src, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts);
+    launch_tonemap(L, src, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, meter_in_front(c, L, src, 1 + (int)slot));
     if (int rc = overlay_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // hover / selection (crh_pick.cpp)
   }
   CRH_HIP(hipGetLastError());
@@ -103,6 +138,77 @@ int crh_read_ldr_begin(crh_ctx* c) { return read_begin(c, false); }
 int crh_read_ldr_end(crh_ctx* c, uint8_t* out) { return read_end(c, out, false); }
 int crh_read_hdr_begin(crh_ctx* c) { return read_begin(c, true); }
 int crh_read_hdr_end(crh_ctx* c, float* out) { return read_end(c, out, true); }
+
+// ---- display state without a restart, auto exposure (reference: the exposure / white point sliders and the tone-mapping combo only write fields the display pass
+// reads, SettingsWidget.cxx:343-404).  None of these calls do_reset.
+int crh_set_display(crh_ctx* c, int tonemap_mode, float exposure, float white_point)
+{
+  if (!c) return CRH_E_INVALID;
+  const float f[] = {exposure, white_point};
+  if (!all_finite(f, 2)) return fail(c, CRH_E_INVALID, "exposure / white point hold a NaN / Inf");
+  c->par.tonemap_mode = tonemap_mode; c->par.exposure = exposure; c->par.white_point = white_point;      // read by the tone map only
+  return CRH_OK;
+}
+
+int crh_get_display(crh_ctx* c, int* tonemap_mode, float* exposure, float* white_point, int* auto_on)
+{
+  if (!c) return CRH_E_INVALID;
+  if (tonemap_mode) *tonemap_mode = c->par.tonemap_mode;
+  if (exposure) *exposure = c->par.exposure;
+  if (white_point) *white_point = c->par.white_point;
+  if (auto_on) *auto_on = c->meter_on ? 1 : 0;
+  return CRH_OK;
+}
+
+void crh_meter_defaults(crh_meter_params* p)
+{
+  if (!p) return;
+  p->key_stops = -2.47393118833f;      // log2(0.18)
+  p->min_stops = -10.0f; p->max_stops = 10.0f;
+  p->white_permille = 990u; p->white_min = 1.0f; p->white_max = 10.0f;
+  p->rect[0] = p->rect[1] = p->rect[2] = p->rect[3] = 0u;
+}
+
+int crh_meter_from_histogram(const uint32_t hist[256], const crh_meter_params* p, float gain_exposure_in, float* exposure, float* white_point, uint32_t* white_bin)
+{
+  if (!hist || !p || !exposure || !white_point) return CRH_E_INVALID;
+  const float in[] = {gain_exposure_in, *white_point};
+  if (!meter_params_ok(p) || !all_finite(in, 2)) return CRH_E_INVALID;
+  uint32_t wb = 0, n_lit = 0;
+  meter_rule_host(hist, meter_rule_of(*p, gain_exposure_in, *white_point), exposure, white_point, &wb, &n_lit);
+  if (white_bin) *white_bin = wb;
+  return CRH_OK;
+}
+
+int crh_set_auto_exposure(crh_ctx* c, const crh_meter_params* p)
+{
+  if (!c) return CRH_E_INVALID;
+  if (!p) { c->meter_on = false; return CRH_OK; }
+  if (!meter_params_ok(p)) return fail(c, CRH_E_INVALID, "meter params: NaN / Inf, min_stops > max_stops, white_min > white_max or white_permille > 1000");
+  if (int rc = ensure_meter_blocks(c)) return rc;
+  c->meter_par = *p; c->meter_on = true;
+  return CRH_OK;
+}
+
+int crh_measure_exposure(crh_ctx* c, const crh_meter_params* p, crh_meter_result* out)
+{
+  if (c) c->read_since_render = true;
+  if (!c || !out || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator / null output");
+  crh_meter_params def; crh_meter_defaults(&def);
+  if (!p) p = &def;
+  if (!meter_params_ok(p)) return fail(c, CRH_E_INVALID, "meter params: NaN / Inf, min_stops > max_stops, white_min > white_max or white_permille > 1000");
+  if (int rc = ensure_meter_blocks(c)) return rc;
+  CRH_HIP(hipSetDevice(c->device));
+  Launch L{cstream(c), c->grid, false};
+  meter_image(c, L, c->assembled_valid ? c->d_assembled : c->d_accum, *p, c->d_meter + 3);
+  CRH_HIP(hipGetLastError());
+  DMeter h;
+  CRH_HIP(hipMemcpyAsync(&h, c->d_meter + 3, sizeof h, hipMemcpyDeviceToHost, cstream(c)));
+  CRH_HIP(hipStreamSynchronize(cstream(c)));
+  std::memcpy(out->hist, h.hist, sizeof out->hist);
+  out->n_unsampled = h.n_unsampled; out->n_lit = h.n_lit; out->exposure = h.metered[0]; out->white_point = h.metered[1]; out->white_bin = h.white_bin;
+  return CRH_OK;
+}
 
 int crh_save_accum(crh_ctx* c, float* out, uint32_t* frames_done)
 {

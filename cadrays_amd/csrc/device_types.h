@@ -97,6 +97,18 @@ struct DCounters {          // device-side mirror of crh_stats
   unsigned long long packet_rays, packet_fallback;      // device only (crh_get_packet_stats): camera rays walked as packets, those of them handed to the per-ray fall-back pass
 };
 
+// One metering block (k_meter.h): the luminance histogram of the image an LDR read-out is about to show and what the rule made of it.  Zeroed by a memset
+// in front of k_luma_histogram; k_meter fills the rest; k_tonemap reads `metered`.  17 cache lines, so two blocks never share one.
+struct DMeter {
+  uint32_t hist[256];
+  uint32_t n_unsampled, n_lit, white_bin, pad0_;
+  float metered[2];         // {exposure, white point}
+  uint32_t pad1_[10];
+};
+static_assert(sizeof(DMeter) == 1088, "a metering block is 17 x 64 B");
+// the rule's inputs as k_meter takes them by value: crh_meter_params without the rectangle + the display values in force
+struct MeterRule { float key_stops, min_stops, max_stops; uint32_t white_permille; float white_min, white_max, exposure_in, white_in; };
+
 struct DQueues {
   uint32_t* q[2];           // active path ids, ping-pong
   uint32_t* q_sh;           // path ids with a pending shadow ray

@@ -203,9 +203,11 @@ __device__ __forceinline__ float hable(float x)
 }
 __global__ __launch_bounds__(kBlock) void k_tonemap(const float4* __restrict__ accum, uint8_t* __restrict__ out, uint32_t n,
                                                      int mode, float exposure, float white_point, int gamma22,
-                                                     const uint8_t* __restrict__ tile_mask, uint32_t width, uint32_t tile_size)
+                                                     const uint8_t* __restrict__ tile_mask, uint32_t width, uint32_t tile_size,
+                                                     const float* __restrict__ metered /* nullptr, or {exposure, white point} of the metering in front (k_meter.h) */)
 {
   const uint32_t tiles_x = tile_mask ? (width + tile_size - 1u) / tile_size : 0u;
+  if (metered) { exposure = metered[0]; white_point = metered[1]; }
   const float gain = crh_exp(exposure * 0.69314718056f);
   const float wp = hable(white_point > 0.f ? white_point : 1.0f);
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {

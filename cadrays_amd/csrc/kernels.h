@@ -46,7 +46,13 @@ void launch_adaptive_pick(const Launch&, const float* tile_err, const uint32_t* 
 void launch_tile_error(const Launch&, const DScene&, const float4* accum, const float* m2, float* tile_err,
                        uint32_t* tile_min_count, uint32_t n_tiles_total);
 void launch_tonemap(const Launch&, const float4* accum, uint8_t* out_rgb, uint32_t n_pixels, int mode, float exposure, float white_point, int gamma22,
-                    const uint8_t* tile_mask /* nullptr: no overlay */, uint32_t width, uint32_t tile_size);
+                    const uint8_t* tile_mask /* nullptr: no overlay */, uint32_t width, uint32_t tile_size,
+                    const float* metered = nullptr /* {exposure, white point} in device memory (DMeter::metered) instead of the two arguments */);
+// Auto exposure (k_meter.h): zero `block`, histogram of the luminances of pixels [x0, x0 + rw) x [y0, y0 + rh) of the width-wide image (the rectangle must lie
+// inside it), then the rule on one thread: block->metered = {exposure, white point}.  meter_rule_host: the same rule on the host.
+void launch_meter(const Launch&, const float4* accum, uint32_t width, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, const MeterRule&, DMeter* block);
+int luma_histogram_grid(const Launch&, uint32_t n_pixels);      // workgroups launch_meter gives k_luma_histogram
+void meter_rule_host(const uint32_t* hist256, const MeterRule&, float* exposure, float* white_point, uint32_t* white_bin, uint32_t* n_lit);
 void launch_hdr(const Launch&, const float4* accum, float* out_rgb, uint32_t n_pixels);
 void launch_add4(const Launch&, float4* dst, const float4* src, uint32_t n_float4);
 // overwrite the triangle records at leaf positions pos[0..n) with recs (3 x float4 each): static / moved split of crh_set_transforms

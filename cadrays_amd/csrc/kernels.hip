@@ -30,6 +30,7 @@ namespace {
 #include "k_frame.h"
 #include "k_accumulate.h"
 #include "k_ids.h"
+#include "k_meter.h"
 
 }  // namespace
 
@@ -181,9 +182,9 @@ void launch_adaptive_pick(const Launch& L, const float* tile_err, const uint32_t
   hipLaunchKernelGGL(k_adaptive_pick, dim3(1), dim3(kBlock), 0, L.stream, tile_err, tile_cnt, n_tiles_total, pick0, n_picks, seed, cdf, picked, tiles_out, seeds_out, n_out);
 }
 void launch_tonemap(const Launch& L, const float4* accum, uint8_t* out, uint32_t n, int mode, float exposure, float wp, int gamma22,
-                    const uint8_t* tile_mask, uint32_t width, uint32_t tile_size)
+                    const uint8_t* tile_mask, uint32_t width, uint32_t tile_size, const float* metered)
 {
-  hipLaunchKernelGGL(k_tonemap, dim3(L.grid), dim3(kBlock), 0, L.stream, accum, out, n, mode, exposure, wp, gamma22, tile_mask, width, tile_size);
+  hipLaunchKernelGGL(k_tonemap, dim3(L.grid), dim3(kBlock), 0, L.stream, accum, out, n, mode, exposure, wp, gamma22, tile_mask, width, tile_size, metered);
 }
 void launch_hdr(const Launch& L, const float4* accum, float* out, uint32_t n)
 {
@@ -223,6 +224,22 @@ void launch_overlay(const Launch& L, uint8_t* ldr, const int32_t* obj_px, uint32
   const OverlaySet sel{sel_flags, sel_flags ? n_flags : 0u, -1, sel_rgb[0], sel_rgb[1], sel_rgb[2], sel_alpha};
   const OverlaySet hov{nullptr, 0u, hover, hov_rgb[0], hov_rgb[1], hov_rgb[2], hov_alpha};
   hipLaunchKernelGGL(k_overlay, dim3(min((uint32_t)L.grid, (W * H + kBlock - 1u) / kBlock)), dim3(kBlock), 0, L.stream, ldr, obj_px, W, H, sel, hov);
+}
+// ---- auto exposure (k_meter.h): zero the block, histogram of the rectangle, the rule -- three stream-ordered steps, nothing waits
+int luma_histogram_grid(const Launch& L, uint32_t n_pixels)
+{
+  // at least 16 pixels per thread: every workgroup ends with up to 256 atomics on the block in HBM, so no more of them than the loads need
+  return (int)min((uint32_t)max(L.grid, 1), max(1u, (n_pixels + 16u * kBlock - 1u) / (16u * kBlock)));
+}
+void launch_meter(const Launch& L, const float4* accum, uint32_t width, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, const MeterRule& R, DMeter* block)
+{
+  hipMemsetAsync(block, 0, sizeof(DMeter), L.stream);
+  if (rw && rh) hipLaunchKernelGGL(k_luma_histogram, dim3(luma_histogram_grid(L, rw * rh)), dim3(kBlock), 0, L.stream, accum, width, x0, y0, rw, rh, block);
+  hipLaunchKernelGGL(k_meter, dim3(1), dim3(64), 0, L.stream, block, R);
+}
+void meter_rule_host(const uint32_t* hist, const MeterRule& R, float* exposure, float* white_point, uint32_t* white_bin, uint32_t* n_lit)
+{
+  meter_rule(hist, R, *exposure, *white_point, *white_bin, *n_lit);
 }
 void pixel_centre_ray_host(const DScene& S, uint32_t px, uint32_t py, float o[3], float d[3])
 {

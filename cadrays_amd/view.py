@@ -123,6 +123,18 @@ class View(Backend):
         self.reset()
         return float(r["depth"])
 
+    # ---- display state (SettingsWidget.cxx:343-404): the sliders re-tone the accumulated image, nothing restarts ----
+    def set_display(self, tonemap_mode, exposure, white_point):
+        super().set_display(tonemap_mode, exposure, white_point)
+        if self._params is not None:      # ChangeRenderingParams builds on these: a later restart keeps what the sliders show
+            self._params = dataclasses.replace(self._params, tonemap_mode=int(tonemap_mode), exposure=float(exposure), white_point=float(white_point))
+
+    def AutoExpose(self, **params):
+        """meter the image once (measure_exposure) and apply the result (set_display); returns the measurement"""
+        m = self.measure_exposure(**params)
+        self.set_display(self.get_display()["tonemap_mode"], float(m["exposure"]), float(m["white_point"]))
+        return m
+
     # ---- device-side extras -----------------------------------------------------------------
     def sync(self):
         self._call("sync")
@@ -252,6 +264,21 @@ class View(Backend):
         self._call("debug_bsdf", C.c_int(fn), C.byref(m), a.ctypes.data_as(fp), b.ctypes.data_as(fp), out.ctypes.data_as(fp),
                    C.c_uint32(n), C.c_int(int(two_sided)))
         return out
+
+
+def meter_from_histogram(hist, exposure_in=0.0, white_in=1.0, **params):
+    """crh_meter_from_histogram on the host only (no GPU): (exposure float32, white_point float32, white_bin) of a (256,) uint32 histogram; exposure_in /
+    white_in are the display values in force (the answer when nothing is lit); params as in Backend.set_auto_exposure"""
+    from .binding import meter_params
+    lib = load_library()
+    h = np.ascontiguousarray(hist, np.uint32)
+    assert h.shape == (256,)
+    p = meter_params(**params)
+    e, w, b = C.c_float(0), C.c_float(float(white_in)), C.c_uint32(0)
+    rc = lib.crh_meter_from_histogram(h.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p), C.c_float(float(exposure_in)), C.byref(e), C.byref(w), C.byref(b))
+    if rc != 0:
+        raise BackendError(f"crh_meter_from_histogram -> {rc}")
+    return np.float32(e.value), np.float32(w.value), int(b.value)
 
 
 def build_bvh_host(pos, tri, threads=0):

@@ -306,6 +306,50 @@ CRH_API int crh_read_ldr_end(crh_ctx* ctx, uint8_t* rgb_out);
  * the order they were begun: the oldest one must be ended with the call of its own kind. */
 CRH_API int crh_read_hdr_begin(crh_ctx* ctx);
 CRH_API int crh_read_hdr_end(crh_ctx* ctx, float* rgb_out);
+/* --- display state and auto exposure (crh_readback.cpp, cadrays_amd/csrc/k_meter.h) ------------------------------------------------------------
+ * Tone-map mode, exposure and white point are fields that ONLY the display pass reads: in the reference the three slider bodies are empty
+ * (SettingsWidget.cxx:343-404), moving one re-tones the accumulated image and nothing else.  None of the calls below restarts or touches the accumulation:
+ * accumulator, frame counter, samples traced ahead, the id buffer and crh_stats stay as they are; crh_read_hdr*, crh_save_accum and crh_reduce never see any
+ * of it. */
+/* == the exposure / white point sliders and the tone-mapping combo (SettingsWidget.cxx:343-404): the three values every LDR read-out (crh_read_ldr,
+ * crh_read_ldr_begin / _end) uses from now on.  All three must be finite (CRH_E_INVALID otherwise).  A later crh_set_params restarts as it always did and
+ * takes its own three values. */
+CRH_API int crh_set_display(crh_ctx* ctx, int tonemap_mode, float exposure, float white_point);
+/* what is in force (SettingsWidget.cxx:343-404 reads the same fields back into its widgets): the three display values -- with auto exposure on, the ones
+ * the metering falls back to -- and whether auto exposure is on; any pointer may be NULL */
+CRH_API int crh_get_display(crh_ctx* ctx, int* tonemap_mode, float* exposure, float* white_point, int* auto_on);
+/* The metering rule.  The luminance histogram has 256 bins: bin 0 counts sampled pixels of luminance 0, bin q >= 1 starts at the float
+ * whose bits are (q + 379) << 21 -- four bins per octave from 2^-32 on (denormals fall in bin 1, overflow and +inf in bin 255).  Exposure [stops] = key_stops
+ * minus the mean log2 luminance of the lit pixels (bin centres), clamped to [min_stops, max_stops]; white point = the upper edge of the bin that holds the
+ * white_permille-th thousandth of the lit pixels, times the metered gain, clamped to [white_min, white_max]. */
+typedef struct crh_meter_params {
+  float    key_stops;             /* log2 of the display value the mean luminance is mapped to; default log2(0.18)            */
+  float    min_stops, max_stops;  /* default -10 / +10: the range of the exposure slider (SettingsWidget.cxx:400)               */
+  uint32_t white_permille;        /* default 990; 0 = keep the display white point; at most 1000                                */
+  float    white_min, white_max;  /* default 1 / 10: the range of the white point slider (SettingsWidget.cxx:392)               */
+  uint32_t rect[4];               /* x0, y0, x1, y1: metered pixels [x0, x1) x [y0, y1); empty (default, all zero) = whole frame */
+} crh_meter_params;
+typedef struct crh_meter_result {
+  uint32_t hist[256];
+  uint32_t n_unsampled;           /* pixels of the rectangle without a sample (a.w <= 0): in no bin                             */
+  uint32_t n_lit;                 /* hist[1] + ... + hist[255]                                                                  */
+  float    exposure, white_point;
+  uint32_t white_bin;             /* the bin whose upper edge became the white point; 0: the white point was not metered        */
+} crh_meter_result;
+CRH_API void crh_meter_defaults(crh_meter_params* p);
+/* Host-only, no device needed: the rule the device runs (the same function, compiled for both sides; SettingsWidget.cxx:343-404 are the two sliders it
+ * moves).  gain_exposure_in and *white_point on entry = the display exposure and white point in force: they are the answer when no pixel is lit (and
+ * *white_point when white_permille is 0).  white_bin may be NULL.  NaN / Inf anywhere, min_stops > max_stops, white_min > white_max or
+ * white_permille > 1000: CRH_E_INVALID. */
+CRH_API int crh_meter_from_histogram(const uint32_t hist[256], const crh_meter_params* p, float gain_exposure_in, float* exposure, float* white_point, uint32_t* white_bin);
+/* Auto exposure == a host that moves the two sliders of SettingsWidget.cxx:343-404 itself before every frame it shows: while on, every LDR read-out meters
+ * the image it is about to tone-map -- memset, luminance histogram, rule, tone map, on the stream that read-out uses anyway; nothing goes through the host,
+ * crh_read_ldr_begin still returns at once.  The tone-map MODE stays the display's.  p == NULL switches it off.  A rectangle that does not fit the target at
+ * the time of a read-out is cut to it. */
+CRH_API int crh_set_auto_exposure(crh_ctx* ctx, const crh_meter_params* p);
+/* One-off measurement of the image an LDR read-out would show now, with `p` (NULL: the defaults); synchronous; changes nothing -- feed the result to
+ * crh_set_display (SettingsWidget.cxx:343-404) to get exactly the bytes auto exposure would have produced. */
+CRH_API int crh_measure_exposure(crh_ctx* ctx, const crh_meter_params* p, crh_meter_result* out);
 /* Accumulator checkpoint / resume (SURVEY.md section 5 "checkpoint / resume", 8f rank 4; the reference only keeps the
  * image while paused, AppViewer.cxx:916-920,1045): copy out / restore the float4 accumulator (rgb running mean + per-pixel
  * sample count) together with the whole-frame iteration counter that selects the next frame seed. */
