@@ -77,6 +77,19 @@ class crh_meter_result(C.Structure):
                 ("white_bin", C.c_uint32)]
 
 
+class crh_fit_result(C.Structure):
+    """what crh_fit_view / crh_fit_from_extents report (include/cadrays_hip.h)"""
+    _fields_ = [("extents", C.c_float * 6), ("right", C.c_float * 3), ("up", C.c_float * 3), ("fwd", C.c_float * 3), ("kx", C.c_float), ("ky", C.c_float),
+                ("z_near", C.c_float), ("z_far", C.c_float), ("n_vertices", C.c_uint32), ("binding", C.c_int32)]
+
+    def as_dict(self):
+        import numpy as np
+        d = {n: np.array(getattr(self, n), np.float32) for n in ("extents", "right", "up", "fwd")}
+        d.update({n: np.float32(getattr(self, n)) for n in ("kx", "ky", "z_near", "z_far")})
+        d.update(n_vertices=int(self.n_vertices), binding=int(self.binding))
+        return d
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -84,6 +97,7 @@ SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rul
 METER_DEFAULTS = dict(key_stops=_f32(-2.4739311883324122), min_stops=-10.0, max_stops=10.0, white_permille=990, white_min=1.0, white_max=10.0, rect=(0, 0, 0, 0))      # key: log2(0.18)
 
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
+assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_bsdf) == 128 and C.sizeof(crh_light) == 32 and C.sizeof(crh_spec) == 52
 
 SCHEDULE_AUTO, SCHEDULE_WIDE, SCHEDULE_SMALL, SCHEDULE_STAGED = 0, 1, 2, 3      # crh_set_schedule
@@ -100,4 +114,5 @@ EXPORTS = [
     "crh_get_kernel_timing", "crh_get_packet_stats", "crh_debug_reduce_fake_devices", "crh_get_path_budget", "crh_get_frame_tuning", "crh_get_tile_order", "crh_build_prebuilt", "crh_query_pipeline_capacity", "crh_env_table",
     "crh_camera_rays", "crh_pick", "crh_read_ids", "crh_set_selection", "crh_set_hover", "crh_get_selection_bounds",
     "crh_set_display", "crh_get_display", "crh_meter_defaults", "crh_meter_from_histogram", "crh_set_auto_exposure", "crh_measure_exposure",
+    "crh_fit_view", "crh_fit_extents_host", "crh_fit_from_extents",
 ]

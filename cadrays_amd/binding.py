@@ -48,6 +48,25 @@ def meter_params(**fields):
     return p
 
 
+def camera_struct(cam):
+    """abi.crh_camera of a scenes.Camera (or anything with its fields)"""
+    c = abi.crh_camera()
+    c.eye[:] = [float(x) for x in cam.eye]
+    c.dir[:] = [float(x) for x in cam.dir]
+    c.up[:] = [float(x) for x in cam.up]
+    c.fovy_deg, c.aspect = float(cam.fovy_deg), float(cam.aspect)
+    c.is_ortho, c.ortho_scale = int(cam.is_ortho), float(cam.ortho_scale)
+    c.aperture_radius, c.focal_dist = float(cam.aperture_radius), float(cam.focal_dist)
+    return c
+
+
+def camera_fields(c):
+    """the fields of an abi.crh_camera as keyword arguments of scenes.Camera / dataclasses.replace (float32 values as Python floats: they survive the way back)"""
+    return dict(eye=tuple(float(x) for x in c.eye), dir=tuple(float(x) for x in c.dir), up=tuple(float(x) for x in c.up), fovy_deg=float(c.fovy_deg),
+                aspect=float(c.aspect), is_ortho=bool(c.is_ortho), ortho_scale=float(c.ortho_scale), aperture_radius=float(c.aperture_radius),
+                focal_dist=float(c.focal_dist))
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -160,14 +179,7 @@ class Backend:
             self._call("set_texture", C.c_uint32(slot), _fp(image), C.c_uint32(w), C.c_uint32(h), C.c_uint32(ch))
 
     def set_camera(self, cam):
-        c = abi.crh_camera()
-        c.eye[:] = [float(x) for x in cam.eye]
-        c.dir[:] = [float(x) for x in cam.dir]
-        c.up[:] = [float(x) for x in cam.up]
-        c.fovy_deg, c.aspect = float(cam.fovy_deg), float(cam.aspect)
-        c.is_ortho, c.ortho_scale = int(cam.is_ortho), float(cam.ortho_scale)
-        c.aperture_radius, c.focal_dist = float(cam.aperture_radius), float(cam.focal_dist)
-        self._call("set_camera", C.byref(c))
+        self._call("set_camera", C.byref(camera_struct(cam)))
 
     def set_params(self, p):
         q = abi.crh_params()
@@ -383,6 +395,22 @@ class Backend:
         lo, hi = np.empty(3, np.float32), np.empty(3, np.float32)
         self._call("get_selection_bounds", _fp(lo), _fp(hi))
         return lo, hi
+
+    # -- fitting the view (crh_fit.cpp) ----------------------------------------------------
+    def fit_view(self, n_objects, chosen=None, margin=0.01, cam=None, want_extents=False):
+        """crh_fit_view == FitAll + ZFitAll (AppViewer.cxx:704, 764-767, 788, 886): the camera that frames the chosen objects (flags; None = every displayed
+        object) seen with `cam` (None = the camera in force), on the device.  Sets nothing.  Returns (camera fields as a dict for scenes.Camera /
+        dataclasses.replace, result dict); with want_extents the result carries "object_extents", (n_objects, 6) float32."""
+        f = None if chosen is None else np.ascontiguousarray(np.asarray(chosen) != 0, np.uint8)
+        n = int(n_objects) if f is None else len(f)
+        out, res = abi.crh_camera(), abi.crh_fit_result()
+        ext = np.empty((n, 6), np.float32) if want_extents else None
+        self._call("fit_view", None if cam is None else C.byref(camera_struct(cam)), None if f is None else f.ctypes.data_as(_u8p), C.c_uint32(n),
+                   C.c_float(float(margin)), C.byref(out), C.byref(res), _fp(ext))
+        r = res.as_dict()
+        if want_extents:
+            r["object_extents"] = ext
+        return camera_fields(out), r
 
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):

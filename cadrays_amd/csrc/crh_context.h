@@ -6,6 +6,7 @@
 //   crh_readback.cpp   HDR / LDR read-back (synchronous and asynchronous), accumulator checkpoints, statistics and kernel timing
 //   crh_reduce.cpp     crh_reduce (RCCL over xGMI, or peer copies on one device)
 //   crh_pick.cpp       the first-hit id buffer: camera rays, pick, id read-back, selection / hover state and bounds, the overlay of the LDR read-out
+//   crh_fit.cpp        fit the view to the displayed / chosen objects: vertex extents on the device (fit_kernels.hip), the closed-form rule, the host-only twins
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
@@ -231,6 +232,13 @@ struct PickState {
   int32_t hover = -1; uint8_t hov_rgb[3] = {0, 0, 0}; uint32_t hov_alpha = 0;
 };
 
+// ---- view fitting (crh_fit.cpp): one float4 {x, y, z, object} per vertex on the device, built from pos / tri / tri_obj and uploaded by the FIRST crh_fit_view after
+// the geometry changed (a host that never fits pays no memory and no time); the per-call object table and the records the kernel fills
+struct FitState {
+  float4* d_fit_verts = nullptr; size_t fit_verts_cap = 0; uint32_t fit_n = 0; bool fit_verts_dirty = true;
+  void* d_fit_objs = nullptr; uint32_t* d_fit_rec = nullptr; size_t fit_objs_cap = 0;      // room for that many objects in both
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -241,7 +249,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -333,6 +341,19 @@ uint32_t frame_seed(uint32_t seed, uint32_t n);
 int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // hover / selection over the tone-mapped bytes at d_ldr, enqueued on `on`; nothing at all when neither is set
 void clear_selection(crh_ctx* c);
 void release_pick(crh_ctx* c);
+uint32_t n_pick_objects(const crh_ctx* c);      // a scene handed over without objects is one object, 0
+int pick_stream(crh_ctx* c);                    // the side stream of the id buffer and of crh_fit_view, created on first need
+int fork_from_context(crh_ctx* c);              // ... made to start behind what the setters have put on the context's stream
+int wait_overlay_readers(crh_ctx* c);
+template <class T> int grow(crh_ctx* c, T*& d, size_t bytes)
+{
+  if (d) { CRH_HIP(hipFree(d)); d = nullptr; }
+  CRH_HIP(hipMalloc((void**)&d, bytes));
+  return CRH_OK;
+}
+
+// ---- crh_fit.cpp
+void release_fit(crh_ctx* c);
 
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);

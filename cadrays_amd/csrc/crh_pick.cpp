@@ -10,42 +10,6 @@ using namespace crh::api;
 
 namespace {
 
-uint32_t n_pick_objects(const crh_ctx* c) { return c->tri_obj.empty() ? 1u : c->nO; }      // a scene handed over without objects is one object, 0
-
-int pick_stream(crh_ctx* c)
-{
-  if (c->pk_stream) return CRH_OK;
-  CRH_HIP(hipStreamCreateWithFlags(&c->pk_stream, hipStreamNonBlocking));
-  CRH_HIP(hipEventCreateWithFlags(&c->pk_fork, hipEventDisableTiming));
-  CRH_HIP(hipMalloc((void**)&c->d_pk_cursor, 64));
-  CRH_HIP(hipMalloc((void**)&c->d_pk_counters, sizeof(DCounters)));
-  CRH_HIP(hipMemsetAsync(c->d_pk_counters, 0, sizeof(DCounters), c->pk_stream));
-  return CRH_OK;
-}
-
-// the side stream starts behind whatever the setters have put on the context's stream (scene uploads are stream-ordered there); the frames in flight on the
-// pipeline streams are NOT joined and the schedule's bookkeeping (cstream()) is not touched: they only read the scene, as this does
-int fork_from_context(crh_ctx* c)
-{
-  CRH_HIP(hipEventRecord(c->pk_fork, c->stream_));
-  CRH_HIP(hipStreamWaitEvent(c->pk_stream, c->pk_fork, 0));
-  return CRH_OK;
-}
-
-// an asynchronous LDR read-back may still be running its overlay over the id buffer and the selection flags: wait for those kernels before either is overwritten
-int wait_overlay_readers(crh_ctx* c)
-{
-  if (c->rb_outstanding) for (int k = 0; k < 2; ++k) if (c->rb_tm[k]) CRH_HIP(hipEventSynchronize(c->rb_tm[k]));
-  return CRH_OK;
-}
-
-template <class T> int grow(crh_ctx* c, T*& d, size_t bytes)
-{
-  if (d) { CRH_HIP(hipFree(d)); d = nullptr; }
-  CRH_HIP(hipMalloc((void**)&d, bytes));
-  return CRH_OK;
-}
-
 // The id buffer of the state in force, computed if a change has invalidated it.  Synchronous on its own stream: when this returns, every stream may read it.
 int ensure_ids(crh_ctx* c)
 {
@@ -95,6 +59,35 @@ bool good_rgb_alpha(const uint8_t* rgb, uint32_t alpha) { return rgb && alpha <=
 
 namespace crh {
 namespace api {
+
+uint32_t n_pick_objects(const crh_ctx* c) { return c->tri_obj.empty() ? 1u : c->nO; }      // a scene handed over without objects is one object, 0
+
+int pick_stream(crh_ctx* c)
+{
+  if (c->pk_stream) return CRH_OK;
+  CRH_HIP(hipStreamCreateWithFlags(&c->pk_stream, hipStreamNonBlocking));
+  CRH_HIP(hipEventCreateWithFlags(&c->pk_fork, hipEventDisableTiming));
+  CRH_HIP(hipMalloc((void**)&c->d_pk_cursor, 64));
+  CRH_HIP(hipMalloc((void**)&c->d_pk_counters, sizeof(DCounters)));
+  CRH_HIP(hipMemsetAsync(c->d_pk_counters, 0, sizeof(DCounters), c->pk_stream));
+  return CRH_OK;
+}
+
+// the side stream starts behind whatever the setters have put on the context's stream (scene uploads are stream-ordered there); the frames in flight on the
+// pipeline streams are NOT joined and the schedule's bookkeeping (cstream()) is not touched: they only read the scene, as this does
+int fork_from_context(crh_ctx* c)
+{
+  CRH_HIP(hipEventRecord(c->pk_fork, c->stream_));
+  CRH_HIP(hipStreamWaitEvent(c->pk_stream, c->pk_fork, 0));
+  return CRH_OK;
+}
+
+// an asynchronous LDR read-back may still be running its overlay over the id buffer and the selection flags: wait for those kernels before either is overwritten
+int wait_overlay_readers(crh_ctx* c)
+{
+  if (c->rb_outstanding) for (int k = 0; k < 2; ++k) if (c->rb_tm[k]) CRH_HIP(hipEventSynchronize(c->rb_tm[k]));
+  return CRH_OK;
+}
 
 void clear_selection(crh_ctx* c) { c->sel.clear(); c->sel_any = false; c->sel_dirty = false; c->hover = -1; }
 

@@ -123,6 +123,26 @@ class View(Backend):
         self.reset()
         return float(r["depth"])
 
+    # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
+    def _fit(self, chosen, margin):
+        fields, r = self.fit_view(self._n_objects, chosen, margin)
+        self.set_camera(dataclasses.replace(self._camera, **fields))
+        self.reset()
+        return r
+
+    def FitAll(self, margin=0.01):
+        """View->FitAll() + ZFitAll() (AppViewer.cxx:704, 764-767, 788, 886): frame every displayed object tightly (margin: OCCT's default); sets the fitted
+        camera and, like every camera change, restarts the accumulation.  Returns the result dict (z_near / z_far: the depth range)."""
+        return self._fit(None, margin)
+
+    def FitSelected(self, margin=0.01):
+        """the same over the selected objects"""
+        if not self._selected:
+            raise BackendError("FitSelected: nothing is selected")
+        flags = np.zeros(self._n_objects, np.uint8)
+        flags[sorted(self._selected)] = 1
+        return self._fit(flags, margin)
+
     # ---- display state (SettingsWidget.cxx:343-404): the sliders re-tone the accumulated image, nothing restarts ----
     def set_display(self, tonemap_mode, exposure, white_point):
         super().set_display(tonemap_mode, exposure, white_point)
@@ -279,6 +299,38 @@ def meter_from_histogram(hist, exposure_in=0.0, white_in=1.0, **params):
     if rc != 0:
         raise BackendError(f"crh_meter_from_histogram -> {rc}")
     return np.float32(e.value), np.float32(w.value), int(b.value)
+
+
+def fit_extents_host(verts4, n_objects, cam, width, height, margin=0.01, obj_xform=None):
+    """crh_fit_extents_host on the host only (no GPU): verts4 (n, 4) float32 {x, y, z, object index as int bits}; returns (extents (n_objects, 6) float32,
+    counts (n_objects,) uint32, dict with the frame used: right, up, fwd, kx, ky)"""
+    from .binding import camera_struct
+    lib = load_library()
+    v = np.ascontiguousarray(verts4, np.float32).reshape(-1, 4)
+    xf = None if obj_xform is None else np.ascontiguousarray(obj_xform, np.float32).reshape(-1, 12)
+    assert xf is None or len(xf) == n_objects
+    ext, cnt, res = np.empty((int(n_objects), 6), np.float32), np.empty(int(n_objects), np.uint32), abi.crh_fit_result()
+    fp = C.POINTER(C.c_float)
+    rc = lib.crh_fit_extents_host(v.ctypes.data_as(fp), C.c_uint32(len(v)), None if xf is None else xf.ctypes.data_as(fp), C.c_uint32(int(n_objects)),
+                                  C.byref(camera_struct(cam)), C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_float(float(margin)), ext.ctypes.data_as(fp),
+                                  cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(res))
+    if rc != 0:
+        raise BackendError(f"crh_fit_extents_host -> {rc}")
+    r = res.as_dict()
+    return ext, cnt, {k: r[k] for k in ("right", "up", "fwd", "kx", "ky")}
+
+
+def fit_from_extents(extents, cam, width, height, margin=0.01):
+    """crh_fit_from_extents on the host only (no GPU): the rule alone; returns (camera fields as a dict, result dict)"""
+    from .binding import camera_fields, camera_struct
+    lib = load_library()
+    e = np.ascontiguousarray(extents, np.float32).reshape(6)
+    out, res = abi.crh_camera(), abi.crh_fit_result()
+    rc = lib.crh_fit_from_extents(e.ctypes.data_as(C.POINTER(C.c_float)), C.byref(camera_struct(cam)), C.c_uint32(int(width)), C.c_uint32(int(height)),
+                                  C.c_float(float(margin)), C.byref(out), C.byref(res))
+    if rc != 0:
+        raise BackendError(f"crh_fit_from_extents -> {rc}")
+    return camera_fields(out), res.as_dict()
 
 
 def build_bvh_host(pos, tri, threads=0):

@@ -409,6 +409,49 @@ CRH_API int crh_set_hover(crh_ctx* ctx, int32_t object /* -1 = none */, const ui
  * objects under the CURRENT transforms (erased objects included while they stay selected).  Nothing selected: CRH_E_INVALID. */
 CRH_API int crh_get_selection_bounds(crh_ctx* ctx, float lo[3], float hi[3]);
 
+/* --- fitting the view (crh_fit.cpp, cadrays_amd/csrc/fit_kernels.hip) ------------------------------------------------------------------------------
+ * == V3d_View::FitAll / ZFitAll as the application drives them: AppViewer::FitAll() sets a flag that the frame loop turns into View->FitAll()
+ * (AppViewer.cxx:704, 764-767), the loop calls View->ZFitAll() (:788), the key binding (:886).  A TIGHT fit on the vertices of the chosen objects under their
+ * CURRENT transforms, not on boxes: the eye moves (direction, up, field of view stay) until the vertices just fill the frame less `margin` on the binding axis
+ * and are centred on the other.  One pass over the vertices on the device reduces six maxima per object:
+ *   p = M v, q = p - eye_in, (x, y, z) = q in the camera frame (right, up, fwd as crh_render derives them);   kx = tan(fovy / 2) aspect (1 - margin),
+ *   ky = tan(fovy / 2) (1 - margin), both 0 for an orthographic camera;   extents R, L, U, D, N, F = max of  x - z kx, -x - z kx, y - z ky, -y - z ky, -z, z
+ * in plain float32 (no fused multiply-add; -0.0 sorts below +0.0), so the device, the host twin and a float32 restatement agree bit for bit.  The rule, in double
+ * on those float32 values, every output rounded once:   ex = (R - L) / 2, ey = (U - D) / 2;
+ *   perspective:  zx = -(R + L) / (2 kx), zy = -(U + D) / (2 ky), ez = min(zx, zy, -N - (F + N) / 16)   [binding 0 / 1 / 2: which of the three gave the minimum;
+ *                 the third keeps a sixteenth of the depth extent clear in front of a shape that points at the viewer]
+ *   orthographic: half = max((U + D) / 2, (R + L) / (2 aspect)) / (1 - margin) -> ortho_scale, ez = -N - max(F + N, 2 half)   [binding 1: the vertical term gave
+ *                 the maximum, 0: the horizontal one]
+ *   eye = eye_in + ex right + ey up + ez fwd;  z_near = -N - ez, z_far = F - ez: the depth range ZFitAll is after.
+ * CRH_E_INVALID with a message: no chosen object has a vertex; z_near <= 0 (all chosen vertices coincide); margin outside [0, 0.9]; NaN / Inf anywhere. */
+typedef struct crh_fit_result {
+  float    extents[6];            /* R, L, U, D, N, F of the chosen objects, relative to the INPUT eye                              */
+  float    right[3], up[3], fwd[3];   /* the camera frame used                                                                      */
+  float    kx, ky;                /* the slopes (0, 0: orthographic)                                                                */
+  float    z_near, z_far;         /* depth range of the chosen vertices seen from the fitted eye                                    */
+  uint32_t n_vertices;            /* vertices that contributed (referenced by a triangle of a chosen object)                        */
+  int32_t  binding;               /* which constraint fixed the distance (above)                                                    */
+} crh_fit_result;                 /* 84 B */
+/* == View->FitAll() + ZFitAll() on a running context (AppViewer.cxx:704, 764-767, 788, 886).  cam_in NULL: the camera in force.  chosen: n_objects flags (the
+ * selection, say), NULL: every DISPLAYED object (crh_set_visibility is honoured).  n_objects must be the scene's count (one more after every crh_add_object; a
+ * scene handed over without objects counts as ONE object), CRH_E_INVALID otherwise.  extents_out (or NULL): 6 * n_objects floats, every object's own six values
+ * (-inf six times for an object without a vertex).  Needs a built scene (CRH_E_NOTBUILT).  Runs on the side stream of the id buffer; synchronous.  The vertex
+ * array {x, y, z, object} is built and uploaded by the first call after the geometry changed (crh_build, crh_add_object) and stays resident: a host that never
+ * fits pays nothing.  It does NOT set the camera: hand *cam_out to crh_set_camera (which restarts as it always did).  Accumulator, frame counter, samples traced
+ * ahead, the id buffer's validity, crh_stats and read-backs in flight are not touched. */
+CRH_API int crh_fit_view(crh_ctx* ctx, const crh_camera* cam_in, const uint8_t* chosen, uint32_t n_objects, float margin, crh_camera* cam_out, crh_fit_result* out /* may be NULL */,
+                 float* extents_out /* 6*n_objects or NULL */);
+/* Host-only, no device and no context: the pass of crh_fit_view (AppViewer.cxx:704, 764-767, 788, 886) over caller-supplied vertices -- the same per-vertex
+ * function in a plain loop, one thread.  verts4: 4 floats per vertex {x, y, z, object index as int bits}; an index outside [0, n_objects) (-1: no triangle
+ * references the vertex) is skipped.  obj_xform NULL: every object at the identity.  aspect <= 0 in the camera: width / height.  extents_out: 6 * n_objects
+ * (-inf for an object without a vertex); counts_out (or NULL): contributing vertices per object; frame_out (or NULL): right / up / fwd / kx / ky filled in, the
+ * rest zero.  Vertex coordinates are taken as finite (the scene setters reject others). */
+CRH_API int crh_fit_extents_host(const float* verts4, uint32_t n_vertices, const float* obj_xform /* 12*n_objects or NULL */, uint32_t n_objects, const crh_camera* cam,
+                         uint32_t width, uint32_t height, float margin, float* extents_out, uint32_t* counts_out, crh_fit_result* frame_out);
+/* Host-only: the rule alone (the function crh_fit_view ends with; AppViewer.cxx:704, 764-767, 788, 886) -- from six extents measured relative to cam->eye with
+ * this camera, target size and margin to the fitted camera.  out may be NULL; out->n_vertices is 0. */
+CRH_API int crh_fit_from_extents(const float extents[6], const crh_camera* cam, uint32_t width, uint32_t height, float margin, crh_camera* cam_out, crh_fit_result* out);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
