@@ -272,15 +272,15 @@ void crh_destroy(crh_ctx* c)
   hipSetDevice(c->device);
   hipStreamSynchronize(cstream(c));
   drain_events(c);
-  for (auto& q : c->feed_tune.pend) { c->ev_pool.push_back(q.e0); c->ev_pool.push_back(q.e1); }
-  for (auto& q : c->tile_order.pend) { hipEventDestroy(q.e0); hipEventDestroy(q.e1); }
-  c->tile_order.pend.clear();
+  for (auto& q : c->feed_tune.t.pend) { c->ev_pool.push_back(q.e0); c->ev_pool.push_back(q.e1); }
+  for (auto& q : c->tile_order.t.pend) { hipEventDestroy(q.e0); hipEventDestroy(q.e1); }
+  c->tile_order.t.pend.clear();
   if (c->pipe_resized) hipEventDestroy(c->pipe_resized);
   if (c->d_tile_ids2) hipFree(c->d_tile_ids2);
   if (c->tile_order.d_cost) hipFree(c->tile_order.d_cost);
   if (c->tile_order.h_cost) hipHostFree(c->tile_order.h_cost);
   if (c->tile_order.copied) hipEventDestroy(c->tile_order.copied);
-  c->feed_tune.pend.clear();
+  c->feed_tune.t.pend.clear();
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
   void* ptrs[] = {c->d_nodes, c->d_pnodes, c->d_tris, c->d_shade, c->d_mats, c->d_lights, c->d_env, c->d_accum, c->paths.ray_o[0], c->paths.ray_d[0], c->paths.ray_o[1], c->paths.ray_d[1], c->paths.thr[1],
                   c->paths.hit, c->paths.thr[0], c->paths.rad, c->paths.sh_o, c->paths.sh_d, c->paths.sh_c,
@@ -317,8 +317,8 @@ int crh_get_frame_tuning(crh_ctx* c, uint32_t out[5])
 {
   if (!c || !out) return fail(c, CRH_E_INVALID, "null argument");
   const crh_ctx::FeedTune& ft = c->feed_tune;
-  out[0] = ft.on ? 1u : 0u; out[1] = ft.on ? ft.chosen : c->frame_feeders; out[2] = ft.n[0] + ft.n[1];
-  out[3] = ft.n[0] ? (uint32_t)(1.0e3 * ft.ms[0] / ft.n[0]) : 0u; out[4] = ft.n[1] ? (uint32_t)(1.0e3 * ft.ms[1] / ft.n[1]) : 0u;
+  out[0] = ft.on ? 1u : 0u; out[1] = ft.on ? ft.chosen : c->frame_feeders; out[2] = ft.t.n[0] + ft.t.n[1];
+  out[3] = ft.t.n[0] ? (uint32_t)(1.0e3 * ft.t.ms[0] / ft.t.n[0]) : 0u; out[4] = ft.t.n[1] ? (uint32_t)(1.0e3 * ft.t.ms[1] / ft.t.n[1]) : 0u;
   return CRH_OK;
 }
 
@@ -326,11 +326,11 @@ int crh_get_tile_order(crh_ctx* c, uint32_t* order, uint32_t* n_tiles, uint64_t 
 {
   if (!c) return CRH_E_INVALID;
   const uint32_t ts = c->par.tile_size;
-  const uint32_t nt = ts ? ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts) : 0u;
+  const uint32_t nt = ts ? plan::tile_count(c->par.width, c->par.height, ts) : 0u;
   const bool have = c->tile_order.on && c->tile_order.order.size() == nt;
   if (order) for (uint32_t t = 0; t < nt; ++t) order[t] = have ? c->tile_order.order[t] : t;
   if (n_tiles) *n_tiles = nt;
-  if (counts) { counts[0] = c->tile_order.reorders; counts[1] = c->tile_order.calls_sorted; counts[2] = c->tile_order.calls_row_major; counts[3] = c->tile_order.frames_collected; counts[4] = c->tile_order.on ? c->tile_order.verdict : 2u; counts[5] = c->tile_order.tn[0] ? (uint64_t)(1.0e3 * c->tile_order.tms[0] / c->tile_order.tn[0]) : 0; counts[6] = c->tile_order.tn[1] ? (uint64_t)(1.0e3 * c->tile_order.tms[1] / c->tile_order.tn[1]) : 0; }
+  if (counts) { counts[0] = c->tile_order.reorders; counts[1] = c->tile_order.calls_sorted; counts[2] = c->tile_order.calls_row_major; counts[3] = c->tile_order.frames_collected; counts[4] = c->tile_order.on ? c->tile_order.verdict : 2u; counts[5] = c->tile_order.t.n[0] ? (uint64_t)(1.0e3 * c->tile_order.t.ms[0] / c->tile_order.t.n[0]) : 0; counts[6] = c->tile_order.t.n[1] ? (uint64_t)(1.0e3 * c->tile_order.t.ms[1] / c->tile_order.t.n[1]) : 0; }
   return CRH_OK;
 }
 

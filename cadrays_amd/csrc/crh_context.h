@@ -2,7 +2,10 @@
 //
 //   crh_context.cpp    create / destroy, device-memory and event helpers, accumulator, crh_reset / crh_sync, the CRH_* environment table
 //   crh_scene.cpp      geometry, transforms, materials, lights, environment, textures, camera, params, spec; crh_build; the kernels' DScene
-//   crh_schedule.cpp   the wavefront schedule: lanes, batches, frame pipelining, look-ahead, adaptive iterations; crh_render / crh_render_tiles
+//   crh_plan.h         the RULES of the schedule as pure functions (no HIP, no context): frame seeds, the cut of a wide call, grids, the frame pipeline's plan,
+//                      the tile order, the two-sided measurement tally; checked on the CPU by tests/schedule_plan_model.cpp
+//   crh_schedule.cpp   the wavefront schedule: lanes, batches, frame pipelining, look-ahead, adaptive iterations -- asks crh_plan.h, enqueues the HIP work;
+//                      crh_render / crh_render_tiles
 //   crh_readback.cpp   HDR / LDR read-back (synchronous and asynchronous), accumulator checkpoints, statistics and kernel timing
 //   crh_reduce.cpp     crh_reduce (RCCL over xGMI, or peer copies on one device)
 //   crh_pick.cpp       the first-hit id buffer: camera rays, pick, id read-back, selection / hover state and bounds, the overlay of the LDR read-out
@@ -28,6 +31,7 @@
 #include "../../include/cadrays_hip.h"
 #include "../../include/crh_xform.h"
 #include "bvh_builder.h"
+#include "crh_plan.h"
 #include "kernels.h"
 
 namespace crh {
@@ -117,10 +121,7 @@ struct ScheduleState {
   // that are still in flight to have added their last counts (render_impl, frame pipeline).
   DCounters* d_counters = nullptr; DCounters* d_counters_ring = nullptr; uint32_t counter_epoch = 0; hipEvent_t counters_zeroed[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t reset_ev = nullptr; bool reset_pending = false;       // crh_reset's memsets of the accumulator: the next frame's ACCUMULATE waits for them, its tracing does not
-  uint64_t stream_uses = 0;                                        // cstream() calls (anything enqueued on the context's stream) ...
-  uint64_t lane_stream_uses[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};      // ... and the count at which each pipeline stream last forked from it
-  uint32_t lane_counter_epoch[8] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u};                    // the accumulation whose counter block each pipeline stream has waited for
-  bool pipe_running[8] = {false, false, false, false, false, false, false, false};      // a frame was submitted on that pipeline stream and has not been seen finished (the frames-in-flight estimate)
+  uint64_t stream_uses = 0;                                        // cstream() calls (anything enqueued on the context's stream)
   uint32_t* d_api_cursor = nullptr;   // work cursor of the API-level trace kernels
   void* d_scratch = nullptr; size_t scratch_bytes = 0;
   bool clamp_grid = true;   // persistent traversal grids are clamped to what the register budget keeps resident (kernels.hip, resident_grid)
@@ -137,13 +138,12 @@ struct ScheduleState {
   hipStream_t lane_stream[8] = {}; hipEvent_t lane_fork = nullptr, lane_join[8] = {}; uint32_t* d_lane_counts = nullptr;
   std::vector<uint32_t> h_tile_ids;      // what d_tile_ids holds (an unchanged tile list is not uploaded again)
   std::vector<uint32_t> h_tile_ids2;     // ... and d_tile_ids2
-  // frame pipelining: consecutive small whole batches (one Redraw() each) run on alternating streams and path-state halves, so
+  // frame pipelining: consecutive small whole batches (one Redraw() each) rotate through pipe_depth streams and path-state slices, so
   // the drain-bound late bounces of frame n overlap the throughput-bound first bounces of frame n + 1; accumulation stays in
-  // frame order (an event between the two accumulate launches)
-  bool pipeline = true; bool pipe_pending[8] = {false, false, false, false, false, false, false, false}; uint32_t pipe_seq = 0; int pipe_div = 4096;
-  uint64_t pipe_total = 0;         // batch size of the frames in flight (their path-state slices are laid out by it)
-  hipEvent_t pipe_resized = nullptr; bool pipe_resized_pending = false;      // complete when the last frame of the PREVIOUS batch size is done (render_impl)
-  uint32_t pipe_last_depth = 0;    // frames in flight the last pipelined frame was submitted with
+  // frame order (an event between consecutive accumulate launches); the rules: crh_plan.h plan_frame
+  bool pipeline = true; int pipe_div = 4096;
+  plan::PipeState pipe;            // what the pipeline's rules remember from frame to frame (crh_plan.h plan_frame)
+  hipEvent_t pipe_resized = nullptr;      // complete when the last frame of the PREVIOUS batch size is done (plan_frame)
   std::chrono::steady_clock::time_point pipe_last_submit{};      // when the previous pipelined frame was submitted
   int pipe_grid_min = 192, pipe_grid_min_shade = 512;      // floors of a pipelined frame's traversal / streaming grids
   uint32_t pipe_depth = 3;         // frames in flight: 2 / 3 / 4 -> 323 / 391 / 312 Redraw/s on C3, 448 / 558 / 453 on C2
@@ -169,10 +169,9 @@ struct ScheduleState {
   // target size or the depth) the first pipelined frame-kernel frames run in blocks of 6 -- a warm-up block, then 3 / 4 / 3 / 4 feeders; the device time of each
   // frame KERNEL (its own event pair, first frame of a block left out) decides: 4 if that is >= 5 % faster, else 3 (CAD1M: 16 %; the soups: within +- 3 %).  No image depends on the count (tests/test_frame_kernel.py).
   struct FeedTune {
-    bool on = true; uint32_t chosen = 0, frames = 0, n[2] = {0, 0}; double ms[2] = {0.0, 0.0};
-    struct Pend { hipEvent_t e0, e1; int which; };
-    std::deque<Pend> pend;
-    void restart() { chosen = 0; frames = 0; n[0] = n[1] = 0; ms[0] = ms[1] = 0.0; for (Pend& q : pend) q.which = -1; }
+    bool on = true; uint32_t chosen = 0, frames = 0;
+    plan::Tally<hipEvent_t> t;      // [0]: 3 feeders, [1]: 4
+    void restart() { chosen = 0; frames = 0; t.restart(); }
   } feed_tune;
   // The ORDER in which a lone frame's tiles are claimed (round 6; CRH_TILE_ORDER=0: row-major as up to round 5).  Whatever the frame kernel claims last runs out its
   // bounces on an emptying chip (the drain is 0.43 of a lone frame); pixels do not depend on the order (the RNG is seeded per pixel).  k_accumulate sums the rays
@@ -185,16 +184,14 @@ struct ScheduleState {
     uint32_t* d_cost = nullptr; uint32_t* h_cost = nullptr; uint32_t n = 0;     // per tile id: rays since the last restart (device), the last restart's copy (pinned host)
     hipEvent_t copied = nullptr; bool pending = false, dirty = false;           // a copy is under way; frames have added to d_cost since the last copy
     std::vector<uint8_t> cls; std::vector<uint32_t> order;                      // the classes the current list was made from; the list (empty: row-major)
-    uint64_t reorders = 0, calls_sorted = 0, calls_row_major = 0, frames_collected = 0; uint32_t streak = 0;
+    uint64_t reorders = 0, calls_sorted = 0, calls_row_major = 0, frames_collected = 0; uint32_t streak = 0;      // streak: crh_render calls in a row that found no frame in flight
     // ... and whether the sorted list pays on THIS scene is measured, once per crh_build (a soup that does not fit the caches loses more by the scattered tiles than
     // the shorter drain gives back: C5's lone 4K frame 10.9 -> 12.1 ms): once a sorted list exists and the feeder count is settled, lone frames take the two lists
     // in turn, each frame kernel between two events; sorted stays if its mean is >= 2 % shorter.  verdict: 0 measuring, 1 sorted, 2 row-major.
-    uint32_t verdict = 0, trials = 0, tn[2] = {0, 0}; double tms[2] = {0.0, 0.0}; int tag_next = -1;
-    struct Pend { hipEvent_t e0, e1; int which; };
-    std::deque<Pend> pend;
-    void remeasure() { verdict = 0; trials = 0; tn[0] = tn[1] = 0; tms[0] = tms[1] = 0.0; tag_next = -1; for (Pend& q : pend) q.which = -1; }                                 // crh_render calls in a row that found no frame in flight
+    uint32_t verdict = 0, trials = 0; int tag_next = -1;
+    plan::Tally<hipEvent_t> t;      // [0]: sorted, [1]: row-major
+    void remeasure() { verdict = 0; trials = 0; tag_next = -1; t.restart(); }
   } tile_order;
-  uint32_t last_running = 0;                        // frames in flight when the last pipelined frame was submitted (render_impl)
   uint32_t frame_help = 256;                        // a tracer wavefront shades a batch itself once this many hit records wait
   uint32_t frame_help_low = 0;                      // ... and prefers a full shading batch to tracing while fewer rays than this wait (CRH_FRAME_HELP_LOW)
   int frame_grid = 0;                               // workgroups of a lone frame (0: what is resident, 4 per CU)
@@ -261,12 +258,11 @@ struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::Fram
   std::string err;
 };
 
-// The context's stream.  Small whole-frame batches alternate between two pipeline streams (render_impl) and are joined lazily:
+// The context's stream.  Small whole-frame batches rotate through the pipeline streams (crh_plan.h plan_frame) and are joined lazily:
 // whoever wants to enqueue on, or wait for, the context's stream first makes it wait for the frames still in flight.
 static inline hipStream_t cstream(crh_ctx* c)
 {
-  for (int k = 0; k < 8; ++k)
-    if (c->pipe_pending[k]) { hipStreamWaitEvent(c->stream_, c->lane_join[k], 0); c->pipe_pending[k] = false; }
+  crh::plan::join_pending(c->pipe, [c](uint32_t k) { hipStreamWaitEvent(c->stream_, c->lane_join[k], 0); });
   if (c->rb_guard_pending) { hipStreamWaitEvent(c->stream_, c->rb_guard, 0); c->rb_guard_pending = false; }      // an asynchronous read-back still tone-maps the accumulator
   c->read_since_render = true;      // something other than the next frame used the stream (render_impl clears this when it is done)
   ++c->stream_uses;
@@ -334,9 +330,6 @@ template <class T> int dev_put(crh_ctx* c, T*& dptr, size_t& cap, const void* sr
 void fill_scene(const crh_ctx* c, DScene& S);
 int upload_textures(crh_ctx* c);
 
-// ---- crh_schedule.cpp
-uint32_t frame_seed(uint32_t seed, uint32_t n);
-
 // ---- crh_pick.cpp
 int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // hover / selection over the tone-mapped bytes at d_ldr, enqueued on `on`; nothing at all when neither is set
 void clear_selection(crh_ctx* c);
@@ -349,6 +342,15 @@ template <class T> int grow(crh_ctx* c, T*& d, size_t bytes)
 {
   if (d) { CRH_HIP(hipFree(d)); d = nullptr; }
   CRH_HIP(hipMalloc((void**)&d, bytes));
+  return CRH_OK;
+}
+// A uint32_t device array that kernels on the context's stream may still read: room for n words (the old contents are gone when it had to grow)
+inline int grow_u32(crh_ctx* c, uint32_t*& d, uint32_t& cap, uint32_t n)
+{
+  if (n <= cap) return CRH_OK;
+  CRH_HIP(hipStreamSynchronize(cstream(c)));
+  if (int rc = grow(c, d, sizeof(uint32_t) * n)) return rc;
+  cap = n;
   return CRH_OK;
 }
 

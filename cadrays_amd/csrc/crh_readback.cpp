@@ -99,7 +99,7 @@ static int read_begin(crh_ctx* c, bool hdr)
   const uint32_t slot = c->rb_head & 1u;
   // everything submitted so far comes first: the frames in flight on the pipeline streams (not joined, they stay in flight) and
   // whatever sits on the context's stream
-  for (int k = 0; k < 8; ++k) if (c->pipe_pending[k]) CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->lane_join[k], 0));
+  for (int k = 0; k < 8; ++k) if (c->pipe.pipe_pending[k]) CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->lane_join[k], 0));
   CRH_HIP(hipEventRecord(c->rb_fork, c->stream_));
   CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->rb_fork, 0));
   Launch L{c->rb_stream, c->grid, false};

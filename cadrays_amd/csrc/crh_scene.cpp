@@ -434,7 +434,7 @@ int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* 
     const size_t cap = (size_t)c->n_pos + (size_t)reserved + 2 * (size_t)nT + c->cap_pos / 4;
     int rc;
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    for (int k = 0; k < 8; ++k) if (c->pipe_pending[k]) CRH_HIP(hipEventSynchronize(c->lane_join[k]));      // frames in flight still read the old arrays
+    for (int k = 0; k < 8; ++k) if (c->pipe.pipe_pending[k]) CRH_HIP(hipEventSynchronize(c->lane_join[k]));      // frames in flight still read the old arrays
     if ((rc = grow_positions(c, c->d_tris, kTriStride, c->n_pos, cap))) return rc;
     if ((rc = grow_positions(c, c->d_shade, 4, c->n_pos, cap))) return rc;
     if (c->d_uvs && (rc = grow_positions(c, c->d_uvs, 2, c->n_pos, cap))) return rc;
