@@ -90,6 +90,16 @@ class crh_fit_result(C.Structure):
         return d
 
 
+class crh_region_stats(C.Structure):
+    """one record of crh_query_region / crh_region_stats_host (include/cadrays_hip.h): an object's (or the background's) pixels inside the region and in the frame,
+    the half-open screen box and the depth range of the pixels inside"""
+    _fields_ = [("pixels", C.c_uint32), ("pixels_frame", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32),
+                ("t_min", C.c_float), ("t_max", C.c_float)]
+
+
+REGION_TOUCHED, REGION_ENCLOSED = 0, 1      # crh_region_select
+REGION_STATS_DTYPE = [("pixels", "<u4"), ("pixels_frame", "<u4"), ("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4"), ("t_min", "<f4"), ("t_max", "<f4")]   # numpy view of the records
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -98,6 +108,7 @@ METER_DEFAULTS = dict(key_stops=_f32(-2.4739311883324122), min_stops=-10.0, max_
 
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
+assert C.sizeof(crh_region_stats) == 32
 assert C.sizeof(crh_bsdf) == 128 and C.sizeof(crh_light) == 32 and C.sizeof(crh_spec) == 52
 
 SCHEDULE_AUTO, SCHEDULE_WIDE, SCHEDULE_SMALL, SCHEDULE_STAGED = 0, 1, 2, 3      # crh_set_schedule
@@ -115,4 +126,5 @@ EXPORTS = [
     "crh_camera_rays", "crh_pick", "crh_read_ids", "crh_set_selection", "crh_set_hover", "crh_get_selection_bounds",
     "crh_set_display", "crh_get_display", "crh_meter_defaults", "crh_meter_from_histogram", "crh_set_auto_exposure", "crh_measure_exposure",
     "crh_fit_view", "crh_fit_extents_host", "crh_fit_from_extents",
+    "crh_query_region", "crh_region_stats_host", "crh_region_select",
 ]

@@ -67,6 +67,14 @@ def camera_fields(c):
                 focal_dist=float(c.focal_dist))
 
 
+def region_args(rect, poly):
+    """(rect pointer or None, polygon pointer or None, vertex count, the arrays kept alive) for crh_query_region / crh_region_stats_host: rect = (x0, y0, x1, y1)
+    half-open or None = the whole frame; poly = (n, 2) integer pixel-corner vertices or None"""
+    r = None if rect is None else np.ascontiguousarray(rect, np.uint32).reshape(4)
+    q = None if poly is None else np.ascontiguousarray(poly, np.int32).reshape(-1, 2)
+    return (None if r is None else r.ctypes.data_as(_u32p), None if q is None else q.ctypes.data_as(_i32p), C.c_uint32(0 if q is None else len(q)), (r, q))
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -411,6 +419,15 @@ class Backend:
         if want_extents:
             r["object_extents"] = ext
         return camera_fields(out), r
+
+    # -- region queries on the id buffer (crh_region.cpp) ----------------------------------
+    def query_region(self, n_objects, rect=None, poly=None):
+        """crh_query_region: the records of every object and of the background (last) for the region rect (x0, y0, x1, y1 half-open; None = whole frame) cut by
+        the polygon poly ((n, 2) pixel-corner vertices, even-odd; None = none): a numpy record array of n_objects + 1 entries (abi.REGION_STATS_DTYPE).  Sets nothing."""
+        out = np.zeros(int(n_objects) + 1, abi.REGION_STATS_DTYPE)
+        r, q, n, _keep = region_args(rect, poly)
+        self._call("query_region", r, q, n, out.ctypes.data_as(C.POINTER(abi.crh_region_stats)), C.c_uint32(int(n_objects)))
+        return out
 
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):

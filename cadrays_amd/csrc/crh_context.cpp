@@ -302,6 +302,7 @@ void crh_destroy(crh_ctx* c)
   for (void* q : {(void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) hipFree(q);
   release_comms(c);
   release_fit(c);
+  release_region(c);
   release_pick(c);
   hipStreamDestroy(c->stream_);
   delete c;

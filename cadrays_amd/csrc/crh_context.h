@@ -236,6 +236,11 @@ struct FitState {
   void* d_fit_objs = nullptr; uint32_t* d_fit_rec = nullptr; size_t fit_objs_cap = 0;      // room for that many objects in both
 };
 
+// ---- region queries (crh_region.cpp): the polygon's edges and the per-object records of ONE call, allocated on first need (a host that never asks pays nothing)
+struct RegionState {
+  void* d_rg_edges = nullptr; uint32_t* d_rg_rec = nullptr; size_t rg_rec_cap = 0;      // room for that many records (objects + background)
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -246,7 +251,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -335,7 +340,8 @@ int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // hover / sel
 void clear_selection(crh_ctx* c);
 void release_pick(crh_ctx* c);
 uint32_t n_pick_objects(const crh_ctx* c);      // a scene handed over without objects is one object, 0
-int pick_stream(crh_ctx* c);                    // the side stream of the id buffer and of crh_fit_view, created on first need
+int ensure_ids(crh_ctx* c);                     // the id buffer of the state in force, computed if a change has invalidated it; synchronous on its own stream
+int pick_stream(crh_ctx* c);                    // the side stream of the id buffer, of crh_fit_view and of crh_query_region, created on first need
 int fork_from_context(crh_ctx* c);              // ... made to start behind what the setters have put on the context's stream
 int wait_overlay_readers(crh_ctx* c);
 template <class T> int grow(crh_ctx* c, T*& d, size_t bytes)
@@ -356,6 +362,9 @@ inline int grow_u32(crh_ctx* c, uint32_t*& d, uint32_t& cap, uint32_t n)
 
 // ---- crh_fit.cpp
 void release_fit(crh_ctx* c);
+
+// ---- crh_region.cpp
+void release_region(crh_ctx* c);
 
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);

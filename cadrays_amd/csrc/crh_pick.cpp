@@ -10,6 +10,13 @@ using namespace crh::api;
 
 namespace {
 
+bool good_rgb_alpha(const uint8_t* rgb, uint32_t alpha) { return rgb && alpha <= 255u; }
+
+}  // namespace
+
+namespace crh {
+namespace api {
+
 // The id buffer of the state in force, computed if a change has invalidated it.  Synchronous on its own stream: when this returns, every stream may read it.
 int ensure_ids(crh_ctx* c)
 {
@@ -52,13 +59,6 @@ int ensure_ids(crh_ctx* c)
   c->ids_valid = true; c->ids_w = W; c->ids_h = H;
   return CRH_OK;
 }
-
-bool good_rgb_alpha(const uint8_t* rgb, uint32_t alpha) { return rgb && alpha <= 255u; }
-
-}  // namespace
-
-namespace crh {
-namespace api {
 
 uint32_t n_pick_objects(const crh_ctx* c) { return c->tri_obj.empty() ? 1u : c->nO; }      // a scene handed over without objects is one object, 0
 

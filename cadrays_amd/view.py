@@ -123,6 +123,29 @@ class View(Backend):
         self.reset()
         return float(r["depth"])
 
+    # ---- rubber band, lasso, visible objects (crh_region.cpp; OCCT: AIS_InteractiveContext::Select(xmin, ymin, xmax, ymax, view) and its polyline form) ----
+    def _select_region(self, stats, mode, min_pixels, shift):
+        hit = set(int(o) for o in np.flatnonzero(region_select(stats, mode, min_pixels)))
+        self._selected = (self._selected ^ hit) if shift else hit
+        self._push_selection()
+        return set(self._selected)
+
+    def SelectRect(self, x0, y0, x1, y1, mode=abi.REGION_TOUCHED, min_pixels=1, shift=False):
+        """rubber-band selection over the pixels [x0, x1) x [y0, y1): the objects with at least min_pixels visible pixels inside (abi.REGION_TOUCHED), or those
+        whose visible pixels all lie inside (abi.REGION_ENCLOSED), replace the selection; shift toggles them instead (ShiftSelect); returns the selected set.
+        Selection is by visible surface: an object wholly hidden behind others is never selected."""
+        return self._select_region(self.query_region(self._n_objects, (x0, y0, x1, y1)), mode, min_pixels, shift)
+
+    def SelectLasso(self, points, mode=abi.REGION_TOUCHED, min_pixels=1, shift=False):
+        """the same over a polygon of 3 .. 256 pixel-corner vertices (x, y), even-odd"""
+        return self._select_region(self.query_region(self._n_objects, None, points), mode, min_pixels, shift)
+
+    def VisibleObjects(self, min_pixels=1):
+        """{object: record} of the objects with at least min_pixels (>= 1) visible pixels in the frame: a dict of pixels_frame, the screen box (x0, y0, x1, y1,
+        half-open) and the depth range (t_min, t_max) of what is visible of each"""
+        st = self.query_region(self._n_objects)
+        return {int(o): {n: st[n][o].item() for n in st.dtype.names} for o in np.flatnonzero(st["pixels_frame"][:-1] >= max(int(min_pixels), 1))}
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -331,6 +354,34 @@ def fit_from_extents(extents, cam, width, height, margin=0.01):
     if rc != 0:
         raise BackendError(f"crh_fit_from_extents -> {rc}")
     return camera_fields(out), res.as_dict()
+
+
+def region_stats_host(object_px, t_px, n_objects, rect=None, poly=None):
+    """crh_region_stats_host on the host only (no GPU): object_px (H, W) int32 ids (-1: nothing hit), t_px (H, W) float32 first-hit distances; the records as
+    Backend.query_region returns them (n_objects + 1, the background last)"""
+    from .binding import region_args
+    lib = load_library()
+    ob, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == t.shape
+    out = np.zeros(int(n_objects) + 1, abi.REGION_STATS_DTYPE)
+    r, q, n, _keep = region_args(rect, poly)
+    rc = lib.crh_region_stats_host(ob.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]), r, q, n,
+                                   out.ctypes.data_as(C.POINTER(abi.crh_region_stats)), C.c_uint32(int(n_objects)))
+    if rc != 0:
+        raise BackendError(f"crh_region_stats_host -> {rc}")
+    return out
+
+
+def region_select(stats, mode=abi.REGION_TOUCHED, min_pixels=1):
+    """crh_region_select on the host only: flags (n_objects,) uint8 from the records of query_region / region_stats_host (the background record, last, is not looked at)"""
+    lib = load_library()
+    st = np.ascontiguousarray(stats, abi.REGION_STATS_DTYPE)
+    flags = np.zeros(max(len(st) - 1, 0), np.uint8)
+    rc = lib.crh_region_select(st.ctypes.data_as(C.POINTER(abi.crh_region_stats)), C.c_uint32(len(flags)), C.c_int(int(mode)), C.c_uint32(int(min_pixels)),
+                               flags.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise BackendError(f"crh_region_select -> {rc}")
+    return flags
 
 
 def build_bvh_host(pos, tri, threads=0):

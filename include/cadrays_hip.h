@@ -452,6 +452,53 @@ CRH_API int crh_fit_extents_host(const float* verts4, uint32_t n_vertices, const
  * this camera, target size and margin to the fitted camera.  out may be NULL; out->n_vertices is 0. */
 CRH_API int crh_fit_from_extents(const float extents[6], const crh_camera* cam, uint32_t width, uint32_t height, float margin, crh_camera* cam_out, crh_fit_result* out);
 
+/* --- region queries (crh_region.cpp, cadrays_amd/csrc/region_kernels.hip) ---------------------------------------------------------------------------
+ * What the application asks about an AREA of the rendered scene: which objects lie under a dragged rectangle or a lasso, which objects are visible in the frame
+ * at all, how much of the screen each covers, in which screen box and depth range.  The reference selects one object per click (AppViewer.cxx:347-457) and has no
+ * counterpart; in OCCT this is AIS_InteractiveContext::Select(xmin, ymin, xmax, ymax, view) and its polyline form.  All of it is ONE reduction over the first-hit
+ * id buffer of the section above, on the device: integers and extrema only, so the device, the host twin and an integer restatement agree
+ * bit for bit.
+ *   REGION = rectangle, cut to the frame, intersected with the polygon if one is given.  rect = {x0, y0, x1, y1}: pixels [x0, x1) x [y0, y1), row 0 = top; NULL = the
+ *   whole frame; a rectangle reaching beyond the target is cut to it (as the metering rectangle is) and what is left may be empty; x0 > x1 or y0 > y1: CRH_E_INVALID.
+ *   POLYGON (poly_xy = x, y per vertex; NULL with n_poly 0 = none), even-odd, exact in integers: vertices are pixel-CORNER coordinates, pixel (px, py) covers
+ *   [px, px + 1) x [py, py + 1).  3 <= n_poly <= 256 and |coordinate| <= 2^20, anything else CRH_E_INVALID.  In doubled units a vertex is (2x, 2y) and the pixel's
+ *   centre (cx, cy) = (2 px + 1, 2 py + 1), so a centre never shares a row with a vertex.  The pixel is inside iff the number of edges a -> b (the closing edge
+ *   included) with   (a.y < cy) != (b.y < cy)   and   cross * sign(b.y - a.y) > 0,   cross = (b.x - a.x)(cy - a.y) - (cx - a.x)(b.y - a.y) in int64,   is odd.
+ *   Horizontal and zero-length edges never count; a centre exactly ON an edge belongs to the polygon on that edge's right-hand side, so two polygons that share an
+ *   edge never both claim a pixel and never both drop it; an axis-aligned rectangle as a polygon is the half-open rectangle; reversing the polygon changes nothing.
+ *   RECORDS: out[o], o < n_objects, for the pixels whose first hit belongs to object o; out[n_objects] for the background -- the pixels whose ray hit nothing (and
+ *   any id outside [0, n_objects)); its t_min / t_max are 0.  The first-hit distances are taken as finite and >= 0 (the id buffer's are): their float bits order as
+ *   the values do.
+ * SELECTION IS BY VISIBLE SURFACE: an object wholly hidden behind others has pixels_frame == 0 and is selected by neither mode, and CRH_REGION_ENCLOSED compares
+ * with what is VISIBLE of the object in the frame (pixels == pixels_frame), not with its geometry: an object half behind another one is enclosed by a region that
+ * holds all of its visible half. */
+typedef struct crh_region_stats {
+  uint32_t pixels;        /* pixels of the region whose first hit belongs to the object            */
+  uint32_t pixels_frame;  /* the same over the whole frame                                         */
+  uint32_t x0, y0, x1, y1;/* half-open box of the pixels counted in `pixels`; all 0 when pixels==0 */
+  float    t_min, t_max;  /* smallest / largest first-hit distance among them; 0 when pixels==0    */
+} crh_region_stats;       /* 32 B */
+#define CRH_REGION_TOUCHED  0   /* pixels >= max(min_pixels, 1)                                    */
+#define CRH_REGION_ENCLOSED 1   /* ... and pixels == pixels_frame: all that is VISIBLE of it is inside */
+/* (no counterpart in the reference, which selects per click: AppViewer.cxx:347-457; OCCT: AIS_InteractiveContext::Select(xmin, ymin, xmax, ymax, view) / the
+ * polyline form.)  The records of every object and of the background for the region, from the id buffer of the state in force.  n_objects must be the scene's
+ * count as crh_set_selection and crh_fit_view take it (one more after every crh_add_object; a scene handed over without objects counts as ONE object),
+ * CRH_E_INVALID otherwise; out takes n_objects + 1 records.  Needs a built scene (CRH_E_NOTBUILT).  Runs on the side stream of the id buffer; synchronous; a stale
+ * buffer is computed first exactly as crh_pick would.  With an empty region every `pixels` is 0 and pixels_frame is still filled.  It sets NO selection: hand the
+ * flags of crh_region_select to crh_set_selection.  Accumulator, frame counter, samples traced ahead, crh_stats, the selection, the id buffer's validity and
+ * read-backs in flight are not touched. */
+CRH_API int crh_query_region(crh_ctx* ctx, const uint32_t rect[4] /* x0,y0,x1,y1 half-open; NULL = whole frame */, const int32_t* poly_xy /* 2*n_poly or NULL */, uint32_t n_poly,
+                     crh_region_stats* out /* n_objects + 1 */, uint32_t n_objects);
+/* Host-only, no device and no context: the pass of crh_query_region (no counterpart in the reference, AppViewer.cxx:347-457 selects per click) over caller-supplied
+ * planes -- the same rule and the same records in a plain loop, one thread.  object_px: width * height ids, row-major, row 0 = top (-1: nothing hit); t_px: the
+ * first-hit distance per pixel, read only where a pixel is inside the region and hit something.  width, height, n_objects >= 1. */
+CRH_API int crh_region_stats_host(const int32_t* object_px, const float* t_px, uint32_t width, uint32_t height, const uint32_t rect[4], const int32_t* poly_xy, uint32_t n_poly,
+                          crh_region_stats* out /* n_objects + 1 */, uint32_t n_objects);
+/* Host-only: the selection rule (== what AIS_InteractiveContext::Select(xmin, ymin, xmax, ymax, view) decides per object; the reference never calls it,
+ * AppViewer.cxx:347-457).  selected_out[o] = 1 iff stats[o].pixels >= max(min_pixels, 1) and, for CRH_REGION_ENCLOSED, stats[o].pixels == stats[o].pixels_frame.
+ * The background record stats[n_objects] is not looked at.  Any other mode, a NULL or n_objects == 0: CRH_E_INVALID. */
+CRH_API int crh_region_select(const crh_region_stats* stats, uint32_t n_objects, int mode, uint32_t min_pixels, uint8_t* selected_out /* n_objects */);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
