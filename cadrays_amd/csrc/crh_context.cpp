@@ -40,12 +40,7 @@ int stage_copy(crh_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t
   const hipStream_t stream = on ? on : cstream(c);
   BuiltScene::Stage& st = c->stage[c->stage_next++ & 3u];
   if (st.used) CRH_HIP(hipEventSynchronize(st.ev));
-  if (st.cap < bytes) {
-    if (st.p) { CRH_HIP(hipHostFree(st.p)); st.p = nullptr; st.cap = 0; }
-    const size_t want = bytes + bytes / 2 + 4096;
-    CRH_HIP(hipHostMalloc(&st.p, want, hipHostMallocDefault));
-    st.cap = want;
-  }
+  CRH_HIP(st.p.reserve(bytes, bytes / 2 + 4096));
   if (!st.ev) CRH_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
   std::memcpy(st.p, src, bytes);
   CRH_HIP(hipMemcpyAsync(dst, st.p, bytes, hipMemcpyHostToDevice, stream));
@@ -85,45 +80,49 @@ void discard_events(crh_ctx* c)
   c->render_ev.clear(); c->trace_ev.clear();
 }
 
+// The path state: the ONE list of its arrays -- where the kernels' records (DPaths / DQueues, passed by value) keep the raw pointer of path_store[i], and the
+// bytes per path slot.  ensure_paths and crh_set_path_budget read it; the context's destructor releases the storage.
+struct PathSlot { void** raw; size_t elem; };
+static void path_slots(crh_ctx* c, PathSlot (&t)[16])
+{
+  DPaths& P = c->paths; DQueues& Q = c->queues;
+  const PathSlot all[16] = {{(void**)&P.ray_o[0], 16}, {(void**)&P.ray_d[0], 16}, {(void**)&P.hit, 16}, {(void**)&P.thr[0], 16}, {(void**)&P.rad, 16},
+                            {(void**)&P.sh_o, 16}, {(void**)&P.sh_d, 16}, {(void**)&P.sh_c, 16}, {(void**)&Q.q[0], 4}, {(void**)&Q.q[1], 4}, {(void**)&Q.q_sh, 4},
+                            {(void**)&P.ray_o[1], 16}, {(void**)&P.ray_d[1], 16}, {(void**)&P.thr[1], 16}, {(void**)&Q.q2, 4}, {(void**)&Q.q2_sh, 4}};
+  std::copy(all, all + 16, t);
+}
+
 int ensure_paths(crh_ctx* c, uint32_t need)
 {
   if (need <= c->path_cap) return CRH_OK;
   CRH_HIP(hipStreamSynchronize(cstream(c)));
-  void** ptrs[] = {(void**)&c->paths.ray_o[0], (void**)&c->paths.ray_d[0], (void**)&c->paths.hit, (void**)&c->paths.thr[0], (void**)&c->paths.rad,
-                   (void**)&c->paths.sh_o, (void**)&c->paths.sh_d, (void**)&c->paths.sh_c,
-                   (void**)&c->queues.q[0], (void**)&c->queues.q[1], (void**)&c->queues.q_sh,
-                   (void**)&c->paths.ray_o[1], (void**)&c->paths.ray_d[1], (void**)&c->paths.thr[1], (void**)&c->queues.q2, (void**)&c->queues.q2_sh};
-  const size_t sz[] = {16, 16, 16, 16, 16, 16, 16, 16, 4, 4, 4, 16, 16, 16, 4, 4};
+  PathSlot slot[16]; path_slots(c, slot);
   c->path_cap = 0;                                          // stays 0 if an allocation below fails
   for (int i = 0; i < 16; ++i) {
-    if (*ptrs[i]) { CRH_HIP(hipFree(*ptrs[i])); *ptrs[i] = nullptr; }
-    CRH_HIP(hipMalloc(ptrs[i], sz[i] * (size_t)need));
+    const hipError_t e = c->path_store[i].reserve(slot[i].elem * (size_t)need);
+    *slot[i].raw = c->path_store[i];                        // (null after a refusal)
+    CRH_HIP(e);
   }
   CRH_HIP(hipMemsetAsync(c->paths.rad, 0, 16 * (size_t)need, cstream(c)));      // no record carries a batch stamp yet (DPaths::stamp is never 0)
-  if (!c->queues.counts) { CRH_HIP(hipMalloc((void**)&c->queues.counts, kCounts * sizeof(uint32_t))); CRH_HIP(hipMemsetAsync(c->queues.counts, 0, kCounts * sizeof(uint32_t), cstream(c))); }
+  if (!c->d_queue_counts) {
+    CRH_HIP(c->d_queue_counts.reserve(kCounts));
+    c->queues.counts = c->d_queue_counts;
+    CRH_HIP(hipMemsetAsync(c->queues.counts, 0, kCounts * sizeof(uint32_t), cstream(c)));
+  }
   c->path_cap = need;
   return CRH_OK;
 }
 
 uint32_t next_stamp(crh_ctx* c) { if (++c->stamp_counter == 0u) ++c->stamp_counter; return c->stamp_counter; }
 
-int ensure_scratch(crh_ctx* c, size_t bytes)
-{
-  if (bytes <= c->scratch_bytes) return CRH_OK;
-  if (c->d_scratch) { CRH_HIP(hipFree(c->d_scratch)); c->d_scratch = nullptr; }
-  CRH_HIP(hipMalloc(&c->d_scratch, bytes));
-  c->scratch_bytes = bytes;
-  return CRH_OK;
-}
-
 int alloc_accum(crh_ctx* c)
 {
   if (c->d_accum && c->accumW == c->par.width && c->accumH == c->par.height) return CRH_OK;
   CRH_HIP(hipStreamSynchronize(cstream(c)));
-  if (c->d_accum) { CRH_HIP(hipFree(c->d_accum)); c->d_accum = nullptr; }
-  CRH_HIP(hipMalloc((void**)&c->d_accum, sizeof(float4) * (size_t)c->par.width * c->par.height));
-  if (c->d_m2) { CRH_HIP(hipFree(c->d_m2)); c->d_m2 = nullptr; }
-  CRH_HIP(hipMalloc((void**)&c->d_m2, sizeof(float) * (size_t)c->par.width * c->par.height));
+  const size_t n = (size_t)c->par.width * c->par.height;  // another size: another block of exactly that size, a smaller one too
+  c->accumW = c->accumH = 0;                              // (no size is in force until both arrays have the new one)
+  CRH_HIP(c->d_accum.release()); CRH_HIP(c->d_accum.reserve(n));
+  CRH_HIP(c->d_m2.release()); CRH_HIP(c->d_m2.reserve(n));
   c->accumW = c->par.width; c->accumH = c->par.height;
   return CRH_OK;
 }
@@ -250,7 +249,7 @@ crh_ctx* crh_create(int device_ordinal)
   crh_ctx* c = new crh_ctx();
   c->device = device_ordinal;
   if (hipSetDevice(device_ordinal) != hipSuccess || hipStreamCreateWithFlags(&c->stream_, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&c->d_counters_ring, 4 * sizeof(DCounters)) != hipSuccess || hipMalloc((void**)&c->d_api_cursor, 64) != hipSuccess || hipMemsetAsync(c->d_counters_ring, 0, 4 * sizeof(DCounters), cstream(c)) != hipSuccess || hipMemsetAsync(c->d_api_cursor, 0, 64, cstream(c)) != hipSuccess ||
+      c->d_counters_ring.reserve(4) != hipSuccess || c->d_api_cursor.reserve(16) != hipSuccess || hipMemsetAsync(c->d_counters_ring, 0, 4 * sizeof(DCounters), cstream(c)) != hipSuccess || hipMemsetAsync(c->d_api_cursor, 0, 64, cstream(c)) != hipSuccess ||
       hipStreamSynchronize(cstream(c)) != hipSuccess) {
     fprintf(stderr, "crh_create: HIP initialisation failed: %s\n", hipGetErrorString(hipGetLastError()));
     delete c; return nullptr;
@@ -270,42 +269,21 @@ void crh_destroy(crh_ctx* c)
 {
   if (!c) return;
   hipSetDevice(c->device);
-  hipStreamSynchronize(cstream(c));
+  std::vector<hipStream_t> streams(c->lane_stream, c->lane_stream + 8);
+  streams.insert(streams.end(), {c->rb_stream, c->pk_stream, cstream(c)});
+  for (hipStream_t q : streams) if (q) hipStreamSynchronize(q);
+  // events: the timing pairs and tallies go back to the pool, the named ones join them there
   drain_events(c);
   for (auto& q : c->feed_tune.t.pend) { c->ev_pool.push_back(q.e0); c->ev_pool.push_back(q.e1); }
-  for (auto& q : c->tile_order.t.pend) { hipEventDestroy(q.e0); hipEventDestroy(q.e1); }
-  c->tile_order.t.pend.clear();
-  if (c->pipe_resized) hipEventDestroy(c->pipe_resized);
-  if (c->d_tile_ids2) hipFree(c->d_tile_ids2);
-  if (c->tile_order.d_cost) hipFree(c->tile_order.d_cost);
-  if (c->tile_order.h_cost) hipHostFree(c->tile_order.h_cost);
-  if (c->tile_order.copied) hipEventDestroy(c->tile_order.copied);
-  c->feed_tune.t.pend.clear();
-  for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
-  void* ptrs[] = {c->d_nodes, c->d_pnodes, c->d_tris, c->d_shade, c->d_mats, c->d_lights, c->d_env, c->d_accum, c->paths.ray_o[0], c->paths.ray_d[0], c->paths.ray_o[1], c->paths.ray_d[1], c->paths.thr[1],
-                  c->paths.hit, c->paths.thr[0], c->paths.rad, c->paths.sh_o, c->paths.sh_d, c->paths.sh_c,
-                  c->queues.q[0], c->queues.q[1], c->queues.q_sh, c->queues.counts, c->d_tile_ids, c->d_seeds, c->d_counters_ring, c->d_api_cursor, c->d_scratch,
-                  c->d_m2, c->d_tile_err, c->d_tile_cnt, c->d_uvs, c->d_texels, c->d_tex_desc, c->d_inst, c->d_patch, c->d_verts, c->d_ibox, c->queues.q2, c->queues.q2_sh};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (c->d_assembled) hipFree(c->d_assembled);
-  if (c->d_peer_stage) hipFree(c->d_peer_stage);
-  for (BuiltScene::Stage& st : c->stage) { if (st.p) hipHostFree(st.p); if (st.ev) hipEventDestroy(st.ev); }
-  for (int k = 0; k < 8; ++k) { if (c->lane_stream[k]) { hipStreamSynchronize(c->lane_stream[k]); hipStreamDestroy(c->lane_stream[k]); } if (c->lane_join[k]) hipEventDestroy(c->lane_join[k]); }
-  if (c->lane_fork) hipEventDestroy(c->lane_fork);
-  if (c->reset_ev) hipEventDestroy(c->reset_ev);
-  for (hipEvent_t e : c->counters_zeroed) if (e) hipEventDestroy(e);
-  if (c->d_lane_counts) hipFree(c->d_lane_counts);
-  if (c->rb_stream) { hipStreamSynchronize(c->rb_stream); hipStreamDestroy(c->rb_stream); }
-  for (int k = 0; k < 2; ++k) { if (c->d_rb[k]) hipFree(c->d_rb[k]); if (c->h_rb[k]) hipHostFree(c->h_rb[k]); if (c->rb_tm[k]) hipEventDestroy(c->rb_tm[k]); if (c->rb_done[k]) hipEventDestroy(c->rb_done[k]); }
-  if (c->rb_fork) hipEventDestroy(c->rb_fork);
-  if (c->d_meter) hipFree(c->d_meter);
-  for (void* q : {(void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) hipFree(q);
+  for (auto& q : c->tile_order.t.pend) { c->ev_pool.push_back(q.e0); c->ev_pool.push_back(q.e1); }
+  for (BuiltScene::Stage& st : c->stage) c->ev_pool.push_back(st.ev);
+  c->ev_pool.insert(c->ev_pool.end(), c->lane_join, c->lane_join + 8);
+  c->ev_pool.insert(c->ev_pool.end(), c->counters_zeroed, c->counters_zeroed + 4);
+  c->ev_pool.insert(c->ev_pool.end(), {c->rb_tm[0], c->rb_tm[1], c->rb_done[0], c->rb_done[1], c->pipe_resized, c->tile_order.copied, c->lane_fork, c->reset_ev, c->rb_fork, c->pk_fork});
+  for (hipEvent_t e : c->ev_pool) if (e) hipEventDestroy(e);
+  for (hipStream_t q : streams) if (q) hipStreamDestroy(q);
   release_comms(c);
-  release_fit(c);
-  release_region(c);
-  release_pick(c);
-  hipStreamDestroy(c->stream_);
-  delete c;
+  delete c;      // every device and pinned block is a member that releases itself (crh_devmem.h)
 }
 
 const char* crh_last_error(crh_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -349,11 +327,9 @@ int crh_set_path_budget(crh_ctx* c, uint64_t max_paths)
   c->max_paths = (uint32_t)max_paths; c->pending_n = 0;
   if (c->path_cap > c->max_paths) {                      // give the memory back now; the next render allocates what it needs
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    void** ptrs[] = {(void**)&c->paths.ray_o[0], (void**)&c->paths.ray_d[0], (void**)&c->paths.hit, (void**)&c->paths.thr[0], (void**)&c->paths.rad,
-                     (void**)&c->paths.sh_o, (void**)&c->paths.sh_d, (void**)&c->paths.sh_c, (void**)&c->queues.q[0], (void**)&c->queues.q[1], (void**)&c->queues.q_sh,
-                     (void**)&c->paths.ray_o[1], (void**)&c->paths.ray_d[1], (void**)&c->paths.thr[1], (void**)&c->queues.q2, (void**)&c->queues.q2_sh};
-    for (void** q : ptrs) if (*q) { CRH_HIP(hipFree(*q)); *q = nullptr; }
+    PathSlot slot[16]; path_slots(c, slot);
     c->path_cap = 0;
+    for (int i = 0; i < 16; ++i) { *slot[i].raw = nullptr; CRH_HIP(c->path_store[i].release()); }
   }
   return CRH_OK;
 }

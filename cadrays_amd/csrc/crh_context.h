@@ -1,6 +1,8 @@
 // crh_context.h -- the context behind the C ABI of libcadrays_hip.so (include/cadrays_hip.h) and the helpers its translation units share.
 //
 //   crh_context.cpp    create / destroy, device-memory and event helpers, accumulator, crh_reset / crh_sync, the CRH_* environment table
+//   crh_devmem.h       who owns device / pinned memory: Buf<T, Mem>, a pointer and its capacity that change together (no HIP, no context); the two HIP
+//                      memory policies, DevBuf<T> and PinnedBuf<T> are below; checked on the CPU by tests/devmem_model.cpp
 //   crh_scene.cpp      geometry, transforms, materials, lights, environment, textures, camera, params, spec; crh_build; the kernels' DScene
 //   crh_plan.h         the RULES of the schedule as pure functions (no HIP, no context): frame seeds, the cut of a wide call, grids, the frame pipeline's plan,
 //                      the tile order, the two-sided measurement tally; checked on the CPU by tests/schedule_plan_model.cpp
@@ -31,10 +33,26 @@
 #include "../../include/cadrays_hip.h"
 #include "../../include/crh_xform.h"
 #include "bvh_builder.h"
+#include "crh_devmem.h"
 #include "crh_plan.h"
 #include "kernels.h"
 
 namespace crh {
+
+// ---- device and pinned host memory: the ONLY callers of the HIP allocator (crh_devmem.h; tests/test_cpu_host.py checks that).  A context's buffers are members
+// of these types: they are released with it.  Synchronisation is not theirs: whoever makes a buffer grow first waits for what may still read it.
+struct DeviceMem {
+  using status = hipError_t; static constexpr status ok = hipSuccess;
+  static status alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static status free(void* p) { return hipFree(p); }
+};
+struct PinnedMem {
+  using status = hipError_t; static constexpr status ok = hipSuccess;
+  static status alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static status free(void* p) { return hipHostFree(p); }
+};
+template <class T> using DevBuf = Buf<T, DeviceMem>;
+template <class T> using PinnedBuf = Buf<T, PinnedMem>;
 
 // ---- host copies of the inputs (what the setters received; crh_build and the per-frame setters work from these)
 struct HostInputs {
@@ -66,12 +84,12 @@ struct TwoLevelState {
   std::vector<Obj> objs; std::vector<uint32_t> obj_tris, static_pos, pos_obj;   // pos_obj: object of the triangle at a leaf position >= n_static
   uint32_t n_static = 0, n_static_live = 0, n_pos = 0; float sbmin[3] = {0, 0, 0}, sbmax[3] = {0, 0, 0};
   uint32_t root2 = 0xFFFFFFFFu; float tlas_lo[3] = {0, 0, 0}, tlas_hi[3] = {0, 0, 0};
-  size_t cap_pos = 0;                     // leaf positions the triangle / shading / uv arrays have room for
-  void* d_patch = nullptr; size_t cap_patch = 0;
+  size_t cap_pos = 0;                     // leaf positions the triangle / shading / uv / vertex arrays ALL have room for (each array knows its own size)
+  DevBuf<void> d_patch;
   int split_passes = -1;                  // CRH_SPLIT_PASSES: -1 auto, 0 one walk, 1 two passes
-  float4* d_ibox = nullptr;               // spheres around the instances' world boxes when there are at most kMaxIBox (the "does the ray come near a moved object" test)
+  DevBuf<float4> d_ibox;                  // spheres around the instances' world boxes when there are at most kMaxIBox (the "does the ray come near a moved object" test)
   float usph[4] = {0.f, 0.f, 0.f, 0.f};  // ... and around the bounds of all of them
-  float4* d_inst = nullptr;
+  DevBuf<float4> d_inst;
 };
 
 // ---- the built scene: host tree + leaf-ordered records, and their residency in HBM
@@ -79,28 +97,27 @@ struct BuiltScene {
   QBvh bvh;
   std::vector<float> h_tris;      // 12 floats per triangle, leaf order
   bool built = false;
-  float4* d_pnodes = nullptr; size_t cap_pnodes = 0;      // packet nodes of a single-level scene (128 B per node; kernels.hip k_expand_packet_nodes)
-  float4 *d_nodes = nullptr, *d_tris = nullptr, *d_shade = nullptr, *d_mats = nullptr, *d_lights = nullptr, *d_env = nullptr;
-  float4 *d_uvs = nullptr, *d_texels = nullptr; uint4* d_tex_desc = nullptr;
-  float4* d_verts = nullptr;      // two-level scenes: object-space vertices per leaf position (shading of instance hits)
+  DevBuf<float4> d_pnodes;        // packet nodes of a single-level scene (128 B per node; kernels.hip k_expand_packet_nodes)
+  DevBuf<float4> d_nodes, d_tris, d_shade, d_mats, d_lights, d_env;
+  DevBuf<float4> d_uvs, d_texels; DevBuf<uint4> d_tex_desc;
+  DevBuf<float4> d_verts;         // two-level scenes: object-space vertices per leaf position (shading of instance hits)
   // setters called every GUI frame (material-editor drags MaterialEditor.cxx:331-337, manipulator moves ImRaytraceControls.cxx:58-89)
-  // reuse their device allocations (capacities below) and copy through a small ring of pinned staging buffers on the context's
+  // reuse their device allocations and copy through a small ring of pinned staging buffers on the context's
   // stream: no hipFree / hipMalloc, no device-wide synchronisation, kernels still in flight keep reading the old bytes
-  size_t cap_nodes = 0, cap_inst = 0, cap_mats = 0, cap_lights = 0, cap_env = 0;
-  struct Stage { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } stage[4];
+  struct Stage { PinnedBuf<void> p; hipEvent_t ev = nullptr; bool used = false; } stage[4];
   uint32_t stage_next = 0;
 };
 
 // ---- accumulator, the frame assembled by crh_reduce, adaptive sampler state
 struct FrameState {
-  float4* d_accum = nullptr; uint32_t accumW = 0, accumH = 0;
-  float* d_m2 = nullptr;            // running mean of squared luminance (adaptive sampling only)
+  DevBuf<float4> d_accum; uint32_t accumW = 0, accumH = 0;
+  DevBuf<float> d_m2;               // running mean of squared luminance (adaptive sampling only)
   // crh_reduce: the frame assembled from all shards lives beside the root's own accumulator (rendering continues into that)
-  float4* d_assembled = nullptr; float4* d_peer_stage = nullptr; uint32_t assembledW = 0, assembledH = 0; bool assembled_valid = false;
+  DevBuf<float4> d_assembled, d_peer_stage; uint32_t assembledW = 0, assembledH = 0; bool assembled_valid = false;
   std::vector<ncclComm_t> comms; std::vector<crh_ctx*> comm_ctxs;      // RCCL communicators of the last multi-device group (kept on the root)
-  float* d_tile_err = nullptr; uint32_t* d_tile_cnt = nullptr; uint32_t tile_stat_cap = 0;
+  DevBuf<float> d_tile_err; DevBuf<uint32_t> d_tile_cnt;      // per tile of the image
   bool show_tiles = false; bool picked_valid = false;                                   // ShowSamplingTiles: d_picked marks the tiles of the last adaptive iteration
-  float* d_tile_cdf = nullptr; uint8_t* d_picked = nullptr; uint32_t* d_adapt_n = nullptr;   // adaptive sampler state in HBM (running sum, drawn-tile mask, tile count)
+  DevBuf<float> d_tile_cdf; DevBuf<uint8_t> d_picked; DevBuf<uint32_t> d_adapt_n;   // adaptive sampler state in HBM (running sum, drawn-tile mask, tile count)
   bool adaptive = false; uint32_t adaptive_tiles = 128; uint32_t adaptive_picks = 0;   // NbRayTracingTiles, Halton index
   uint32_t frames_done = 0;       // whole-frame iterations since reset (crh_render continues from here)
 };
@@ -111,19 +128,20 @@ struct ScheduleState {
   // and wait in the path buffer (batch sample index pending_off ...) to be folded in by the next crh_render calls
   uint32_t lookahead = 1, pending_first = 0, pending_n = 0, pending_off = 0, pending_tiles = 0;
   uint32_t lookahead_auto = 0, ramp_k = 1;               // crh_set_lookahead_auto: the batch grows 1, 4, 16, ... after every restart of the accumulation
-  DPaths paths{}; DQueues queues{}; uint32_t path_cap = 0;
+  DPaths paths{}; DQueues queues{}; uint32_t path_cap = 0;      // what the kernels take by value: raw pointers into path_store / d_queue_counts (path_slots())
+  DevBuf<void> path_store[16]; DevBuf<uint32_t> d_queue_counts;
   uint32_t stamp_counter = 0;        // DPaths::stamp of the last batch traced (never 0: the radiance buffer is zeroed when it is allocated)
-  uint32_t* d_tile_ids = nullptr; uint32_t tile_cap = 0;
-  uint32_t* d_tile_ids2 = nullptr; uint32_t tile_cap2 = 0; int tile_list_last = 0;      // render_impl keeps two lists resident (round 6: row-major and sorted)
-  uint32_t* d_seeds = nullptr; uint32_t seed_cap = 0;
+  DevBuf<uint32_t> d_tile_ids;
+  DevBuf<uint32_t> d_tile_ids2; int tile_list_last = 0;      // render_impl keeps two lists resident (round 6: row-major and sorted)
+  DevBuf<uint32_t> d_seeds;
   // Counters of the CURRENT accumulation (crh_stats counts since the last restart).  Four blocks, used in turn: crh_reset moves on to the next one -- zeroed one
   // restart earlier, stream-ordered -- instead of zeroing the one in use, so the first frame after a restart need not wait for the frames of the old accumulation
   // that are still in flight to have added their last counts (render_impl, frame pipeline).
-  DCounters* d_counters = nullptr; DCounters* d_counters_ring = nullptr; uint32_t counter_epoch = 0; hipEvent_t counters_zeroed[4] = {nullptr, nullptr, nullptr, nullptr};
+  DCounters* d_counters = nullptr; DevBuf<DCounters> d_counters_ring; uint32_t counter_epoch = 0; hipEvent_t counters_zeroed[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t reset_ev = nullptr; bool reset_pending = false;       // crh_reset's memsets of the accumulator: the next frame's ACCUMULATE waits for them, its tracing does not
   uint64_t stream_uses = 0;                                        // cstream() calls (anything enqueued on the context's stream)
-  uint32_t* d_api_cursor = nullptr;   // work cursor of the API-level trace kernels
-  void* d_scratch = nullptr; size_t scratch_bytes = 0;
+  DevBuf<uint32_t> d_api_cursor;      // work cursor of the API-level trace kernels
+  DevBuf<void> d_scratch;
   bool clamp_grid = true;   // persistent traversal grids are clamped to what the register budget keeps resident (kernels.hip, resident_grid)
   int packets = 64;         // smallest run of consecutive samples per pixel (sample_group) from which wide batches walk their camera rays as wavefront packets (kernels.hip, k_trace_packets): 64 = a wavefront is ONE pixel (C3 +3.3 % at 128 spp per batch, +1.6 % at 64); with two / four pixels per wavefront (32 / 16 samples each) the shared walk loses (C3 -2 % / -5.6 %); CRH_PACKETS=<n> sets the threshold, 0 switches packets off
   bool donate = true;       // small batches use the work-donating traversal kernels (kernels.hip, DON); CRH_DONATE=0 switches them off
@@ -135,7 +153,7 @@ struct ScheduleState {
   // Measured on C3 at 1080p, 1 spp per call (tools/bench_interactive.py): 1 / 2 / 4 / 8 ranges -> 162 / 175 / 114 / 84 Redraw/s: two
   // concurrent schedules overlap, more of them only add launches that each end in their own ~0.4 ms drain.
   uint32_t n_lanes = 2, lane_max_paths = 12u << 20;
-  hipStream_t lane_stream[8] = {}; hipEvent_t lane_fork = nullptr, lane_join[8] = {}; uint32_t* d_lane_counts = nullptr;
+  hipStream_t lane_stream[8] = {}; hipEvent_t lane_fork = nullptr, lane_join[8] = {}; DevBuf<uint32_t> d_lane_counts;
   std::vector<uint32_t> h_tile_ids;      // what d_tile_ids holds (an unchanged tile list is not uploaded again)
   std::vector<uint32_t> h_tile_ids2;     // ... and d_tile_ids2
   // frame pipelining: consecutive small whole batches (one Redraw() each) rotate through pipe_depth streams and path-state slices, so
@@ -181,7 +199,7 @@ struct ScheduleState {
   // C2, +-1 % on C3; the drag, display and free-running loops unchanged.
   struct TileOrder {
     bool on = true;
-    uint32_t* d_cost = nullptr; uint32_t* h_cost = nullptr; uint32_t n = 0;     // per tile id: rays since the last restart (device), the last restart's copy (pinned host)
+    DevBuf<uint32_t> d_cost; PinnedBuf<uint32_t> h_cost; uint32_t n = 0;        // per tile id: rays since the last restart (device), the last restart's copy (pinned host)
     hipEvent_t copied = nullptr; bool pending = false, dirty = false;           // a copy is under way; frames have added to d_cost since the last copy
     std::vector<uint8_t> cls; std::vector<uint32_t> order;                      // the classes the current list was made from; the list (empty: row-major)
     uint64_t reorders = 0, calls_sorted = 0, calls_row_major = 0, frames_collected = 0; uint32_t streak = 0;      // streak: crh_render calls in a row that found no frame in flight
@@ -205,12 +223,12 @@ struct ScheduleState {
 // accumulate waits (for the tone map, which reads the accumulator), nothing else does
 struct ReadbackState {
   hipStream_t rb_stream = nullptr; hipEvent_t rb_fork = nullptr, rb_tm[2] = {nullptr, nullptr}, rb_done[2] = {nullptr, nullptr};
-  uint8_t* d_rb[2] = {nullptr, nullptr}; uint8_t* h_rb[2] = {nullptr, nullptr}; size_t rb_cap = 0, rb_bytes[2] = {0, 0}; bool rb_hdr[2] = {false, false};
+  DevBuf<uint8_t> d_rb[2]; PinnedBuf<uint8_t> h_rb[2]; size_t rb_bytes[2] = {0, 0}; bool rb_hdr[2] = {false, false};
   uint32_t rb_head = 0, rb_outstanding = 0; bool rb_guard_pending = false; hipEvent_t rb_guard = nullptr;
   // auto exposure (crh_set_auto_exposure; kernels in k_meter.h): while on, every LDR read-out meters the image in front of its tone map, on the stream it uses anyway.
   // Four metering blocks (allocated on first need): [0] the synchronous read-out, [1] / [2] the two read-back slots, [3] crh_measure_exposure -- the context's
   // stream and the read-back stream never share one.  The display values themselves are par.tonemap_mode / exposure / white_point: only the tone map reads them.
-  bool meter_on = false; crh_meter_params meter_par{}; DMeter* d_meter = nullptr;
+  bool meter_on = false; crh_meter_params meter_par{}; DevBuf<DMeter> d_meter;
 };
 
 // ---- the first-hit id buffer (crh_pick.cpp): DERIVED state -- object / triangle / distance under every pixel centre for the camera, target size, geometry, transforms,
@@ -219,26 +237,26 @@ struct ReadbackState {
 // state; only the LDR read-out looks at them.
 struct PickState {
   hipStream_t pk_stream = nullptr; hipEvent_t pk_fork = nullptr;
-  float4* d_pk_rays = nullptr; float4* d_pk_hit_slot = nullptr; size_t pk_cap_slots = 0;     // per ray slot (8x8-block order): the ray, what the traversal kernel answered
-  float4* d_pk_hit = nullptr; int32_t* d_pk_obj = nullptr; size_t pk_cap_px = 0;             // per pixel, row-major: {t, u, v, caller's triangle index}, object
-  int32_t* d_pk_tri_obj = nullptr; size_t pk_tri_obj_cap = 0; bool pk_tri_obj_dirty = true;  // c->tri_obj on the device (uploaded on first need after crh_build / crh_add_object)
-  uint32_t* d_pk_cursor = nullptr; DCounters* d_pk_counters = nullptr;                       // work cursor and counter block of the id pass (crh_stats never sees its rays)
+  DevBuf<float4> d_pk_rays, d_pk_hit_slot;                                                   // per ray slot (8x8-block order): the ray, what the traversal kernel answered
+  DevBuf<float4> d_pk_hit; DevBuf<int32_t> d_pk_obj;                                         // per pixel, row-major: {t, u, v, caller's triangle index}, object
+  DevBuf<int32_t> d_pk_tri_obj; bool pk_tri_obj_dirty = true;                                // c->tri_obj on the device (uploaded on first need after crh_build / crh_add_object)
+  DevBuf<uint32_t> d_pk_cursor; DevBuf<DCounters> d_pk_counters;                             // work cursor and counter block of the id pass (crh_stats never sees its rays)
   bool ids_valid = false; uint32_t ids_w = 0, ids_h = 0;
   std::vector<uint8_t> sel; bool sel_any = false; uint8_t sel_rgb[3] = {0, 0, 0}; uint32_t sel_alpha = 0;
-  uint8_t* d_sel = nullptr; size_t sel_cap = 0; bool sel_dirty = false;
+  DevBuf<uint8_t> d_sel; bool sel_dirty = false;
   int32_t hover = -1; uint8_t hov_rgb[3] = {0, 0, 0}; uint32_t hov_alpha = 0;
 };
 
 // ---- view fitting (crh_fit.cpp): one float4 {x, y, z, object} per vertex on the device, built from pos / tri / tri_obj and uploaded by the FIRST crh_fit_view after
 // the geometry changed (a host that never fits pays no memory and no time); the per-call object table and the records the kernel fills
 struct FitState {
-  float4* d_fit_verts = nullptr; size_t fit_verts_cap = 0; uint32_t fit_n = 0; bool fit_verts_dirty = true;
-  void* d_fit_objs = nullptr; uint32_t* d_fit_rec = nullptr; size_t fit_objs_cap = 0;      // room for that many objects in both
+  DevBuf<float4> d_fit_verts; uint32_t fit_n = 0; bool fit_verts_dirty = true;
+  DevBuf<void> d_fit_objs; DevBuf<uint32_t> d_fit_rec;      // room for the same number of objects in both
 };
 
 // ---- region queries (crh_region.cpp): the polygon's edges and the per-object records of ONE call, allocated on first need (a host that never asks pays nothing)
 struct RegionState {
-  void* d_rg_edges = nullptr; uint32_t* d_rg_rec = nullptr; size_t rg_rec_cap = 0;      // room for that many records (objects + background)
+  DevBuf<void> d_rg_edges; DevBuf<uint32_t> d_rg_rec;      // kRegionMaxEdges edges; kRegionRec words per record (objects + background)
 };
 
 // ---- counters and timing
@@ -292,7 +310,6 @@ int check_device_error(crh_ctx* c);      // CRH_E_DEVICE + message if a frame-ke
 int trim_events(crh_ctx* c);
 void discard_events(crh_ctx* c);
 int ensure_paths(crh_ctx* c, uint32_t need);
-int ensure_scratch(crh_ctx* c, size_t bytes);
 uint32_t next_stamp(crh_ctx* c);     // DPaths::stamp for the batch about to be traced
 int alloc_accum(crh_ctx* c);
 int do_reset(crh_ctx* c);
@@ -303,31 +320,27 @@ uint32_t pipeline_capacity(); // frames crh_set_pipeline_depth accepts in this p
 // Every copy and memset goes through the context's own stream: it is created non-blocking, so work on the null stream (plain
 // hipMemset / hipMemcpy) is NOT ordered with it -- a hipMemset of the queue counters on the null stream used to land in the middle
 // of the first batch of a fresh context when other contexts kept the device busy (lost and doubled paths).
-template <class T> int dev_upload(crh_ctx* c, T*& dptr, const void* src, size_t bytes)
+//
+// Refresh a device array in place: the allocation is kept (and grown with head-room only when it is too small), the bytes travel
+// stream-ordered.  Large blocks (environment maps, whole node arrays) are copied straight from the caller's memory and waited for.
+template <class T> int dev_put(crh_ctx* c, DevBuf<T>& d, const void* src, size_t bytes, size_t headroom = 0)
 {
+  if (bytes > d.bytes() || !d) {
+    CRH_HIP(hipStreamSynchronize(cstream(c)));          // kernels in flight may still read the old allocation
+    CRH_HIP(d.reserve((std::max<size_t>(bytes + headroom, 256) + d.elem - 1) / d.elem));
+  }
+  if (bytes <= (4u << 20)) return stage_copy(c, d, src, bytes);
+  CRH_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
-  if (dptr) { CRH_HIP(hipFree(dptr)); dptr = nullptr; }
-  if (!bytes) return CRH_OK;
-  CRH_HIP(hipMalloc((void**)&dptr, bytes));
-  CRH_HIP(hipMemcpyAsync(dptr, src, bytes, hipMemcpyHostToDevice, cstream(c)));
-  CRH_HIP(hipStreamSynchronize(cstream(c)));            // `src` may be a temporary of the caller
   return CRH_OK;
 }
 
-// Refresh a device array in place: the allocation is kept (and grown with head-room only when it is too small), the bytes travel
-// stream-ordered.  Large blocks (environment maps, whole node arrays) are copied straight from the caller's memory and waited for.
-template <class T> int dev_put(crh_ctx* c, T*& dptr, size_t& cap, const void* src, size_t bytes, size_t headroom = 0)
+// Room for n words in a device array that kernels on the context's stream may still read (the old contents are gone when it had to grow)
+inline int grow_u32(crh_ctx* c, DevBuf<uint32_t>& d, size_t n)
 {
-  if (bytes > cap || !dptr) {
-    CRH_HIP(hipStreamSynchronize(cstream(c)));          // kernels in flight may still read the old allocation
-    if (dptr) { CRH_HIP(hipFree(dptr)); dptr = nullptr; cap = 0; }
-    const size_t want = std::max<size_t>(bytes + headroom, 256);
-    CRH_HIP(hipMalloc((void**)&dptr, want));
-    cap = want;
-  }
-  if (bytes <= (4u << 20)) return stage_copy(c, dptr, src, bytes);
-  CRH_HIP(hipMemcpyAsync(dptr, src, bytes, hipMemcpyHostToDevice, cstream(c)));
+  if (n <= d.cap()) return CRH_OK;
   CRH_HIP(hipStreamSynchronize(cstream(c)));
+  CRH_HIP(d.reserve(n));
   return CRH_OK;
 }
 
@@ -338,34 +351,11 @@ int upload_textures(crh_ctx* c);
 // ---- crh_pick.cpp
 int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // hover / selection over the tone-mapped bytes at d_ldr, enqueued on `on`; nothing at all when neither is set
 void clear_selection(crh_ctx* c);
-void release_pick(crh_ctx* c);
 uint32_t n_pick_objects(const crh_ctx* c);      // a scene handed over without objects is one object, 0
 int ensure_ids(crh_ctx* c);                     // the id buffer of the state in force, computed if a change has invalidated it; synchronous on its own stream
 int pick_stream(crh_ctx* c);                    // the side stream of the id buffer, of crh_fit_view and of crh_query_region, created on first need
 int fork_from_context(crh_ctx* c);              // ... made to start behind what the setters have put on the context's stream
 int wait_overlay_readers(crh_ctx* c);
-template <class T> int grow(crh_ctx* c, T*& d, size_t bytes)
-{
-  if (d) { CRH_HIP(hipFree(d)); d = nullptr; }
-  CRH_HIP(hipMalloc((void**)&d, bytes));
-  return CRH_OK;
-}
-// A uint32_t device array that kernels on the context's stream may still read: room for n words (the old contents are gone when it had to grow)
-inline int grow_u32(crh_ctx* c, uint32_t*& d, uint32_t& cap, uint32_t n)
-{
-  if (n <= cap) return CRH_OK;
-  CRH_HIP(hipStreamSynchronize(cstream(c)));
-  if (int rc = grow(c, d, sizeof(uint32_t) * n)) return rc;
-  cap = n;
-  return CRH_OK;
-}
-
-// ---- crh_fit.cpp
-void release_fit(crh_ctx* c);
-
-// ---- crh_region.cpp
-void release_region(crh_ctx* c);
-
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

@@ -14,8 +14,8 @@ static int trace_api(crh_ctx* c, const float* rays, uint32_t n, int any_hit, flo
   if (!n) return CRH_OK;
   CRH_HIP(hipSetDevice(c->device));
   const size_t in_b = 32 * (size_t)n, out_b = (any_hit ? 4 : 16) * (size_t)n;
-  int rc = ensure_scratch(c, in_b + out_b); if (rc) return rc;
-  char* base = (char*)c->d_scratch;
+  CRH_HIP(c->d_scratch.reserve(in_b + out_b));
+  char* base = c->d_scratch.as<char>();
   CRH_HIP(hipMemcpyAsync(base, rays, in_b, hipMemcpyHostToDevice, cstream(c)));
   DScene S; fill_scene(c, S);
   Launch L{cstream(c), c->grid_trace, c->counters_on, c->clamp_grid ? c->cus : 0};
@@ -35,8 +35,8 @@ int crh_bench_trace(crh_ctx* c, const float* rays, uint32_t n, int any_hit, uint
   if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
   CRH_HIP(hipSetDevice(c->device));
   const size_t in_b = 32 * (size_t)n, out_b = 16 * (size_t)n;
-  int rc = ensure_scratch(c, in_b + out_b); if (rc) return rc;
-  char* base = (char*)c->d_scratch;
+  CRH_HIP(c->d_scratch.reserve(in_b + out_b));
+  char* base = c->d_scratch.as<char>();
   CRH_HIP(hipMemcpyAsync(base, rays, in_b, hipMemcpyHostToDevice, cstream(c)));
   DScene S; fill_scene(c, S);
   Launch L{cstream(c), c->grid_trace, false, c->clamp_grid ? c->cus : 0};
@@ -66,8 +66,8 @@ int crh_debug_math(crh_ctx* c, int fn, const float* a, const float* b, float* ou
   if (!c || !a || !b || !out || !out2 || !n) return fail(c, CRH_E_INVALID, "bad debug_math arguments");
   CRH_HIP(hipSetDevice(c->device));
   const size_t bytes = sizeof(float) * (size_t)n;
-  int rc = ensure_scratch(c, 4 * bytes); if (rc) return rc;
-  float* d = (float*)c->d_scratch;
+  CRH_HIP(c->d_scratch.reserve(4 * bytes));
+  float* d = c->d_scratch.as<float>();
   CRH_HIP(hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, cstream(c)));
   CRH_HIP(hipMemcpyAsync(d + n, b, bytes, hipMemcpyHostToDevice, cstream(c)));
   CRH_HIP(hipMemsetAsync(d + 2 * (size_t)n, 0, 2 * bytes, cstream(c)));
@@ -86,8 +86,8 @@ int crh_debug_bsdf(crh_ctx* c, int fn, const crh_bsdf* m, const float* a, const 
   CRH_HIP(hipSetDevice(c->device));
   const size_t per_out = fn == 2 ? 8 : (fn == 1 ? 1 : 3);
   const size_t in_b = sizeof(float) * 3 * (size_t)n, out_b = sizeof(float) * per_out * (size_t)n;
-  int rc = ensure_scratch(c, 256 + 2 * in_b + out_b); if (rc) return rc;
-  char* base = (char*)c->d_scratch;
+  CRH_HIP(c->d_scratch.reserve(256 + 2 * in_b + out_b));
+  char* base = c->d_scratch.as<char>();
   float* d_a = (float*)(base + 256); float* d_b = (float*)(base + 256 + in_b); float* d_o = (float*)(base + 256 + 2 * in_b);
   CRH_HIP(hipMemcpyAsync(base, m, sizeof(crh_bsdf), hipMemcpyHostToDevice, cstream(c)));
   CRH_HIP(hipMemcpyAsync(d_a, a, in_b, hipMemcpyHostToDevice, cstream(c)));

@@ -130,18 +130,6 @@ void fill_objects(std::vector<FitObject>& tab, const float* xf, uint32_t nO)
 
 }  // namespace
 
-namespace crh {
-namespace api {
-
-void release_fit(crh_ctx* c)
-{
-  for (void* p : {(void*)c->d_fit_verts, c->d_fit_objs, (void*)c->d_fit_rec}) if (p) hipFree(p);
-  c->d_fit_verts = nullptr; c->d_fit_objs = nullptr; c->d_fit_rec = nullptr;
-}
-
-}  // namespace api
-}  // namespace crh
-
 extern "C" {
 
 int crh_fit_view(crh_ctx* c, const crh_camera* cam_in, const uint8_t* chosen, uint32_t n_objects, float margin, crh_camera* cam_out, crh_fit_result* out, float* extents_out)
@@ -165,26 +153,16 @@ int crh_fit_view(crh_ctx* c, const crh_camera* cam_in, const uint8_t* chosen, ui
   if (c->fit_verts_dirty) {                              // the first fit after the geometry changed: build the array and upload it
     std::vector<float> v4; build_fit_verts(c, v4);
     const size_t nV = v4.size() / 4;
-    if (nV > c->fit_verts_cap) {
-      c->fit_verts_cap = 0;
-      const size_t cap = nV + nV / 4;                    // crh_add_object grows it a little at a time
-      if ((rc = grow(c, c->d_fit_verts, sizeof(float4) * cap))) return rc;
-      c->fit_verts_cap = cap;
-    }
+    CRH_HIP(c->d_fit_verts.reserve(nV, nV / 4));        // crh_add_object grows it a little at a time
     if (nV) CRH_HIP(hipMemcpyAsync(c->d_fit_verts, v4.data(), sizeof(float4) * nV, hipMemcpyHostToDevice, c->pk_stream));
     CRH_HIP(hipStreamSynchronize(c->pk_stream));         // v4 is a temporary
     c->fit_n = (uint32_t)nV; c->fit_verts_dirty = false;
   }
-  if (nO > c->fit_objs_cap) {
-    c->fit_objs_cap = 0;
-    const size_t cap = (size_t)nO + 16;
-    if ((rc = grow(c, c->d_fit_objs, sizeof(FitObject) * cap)) || (rc = grow(c, c->d_fit_rec, sizeof(uint32_t) * kFitRec * cap))) return rc;
-    c->fit_objs_cap = cap;
-  }
+  CRH_HIP(c->d_fit_objs.reserve(sizeof(FitObject) * nO, sizeof(FitObject) * 16)); CRH_HIP(c->d_fit_rec.reserve((size_t)kFitRec * nO, (size_t)kFitRec * 16));
   std::vector<uint32_t> rec((size_t)kFitRec * nO, 0u);
   CRH_HIP(hipMemcpyAsync(c->d_fit_objs, tab.data(), sizeof(FitObject) * nO, hipMemcpyHostToDevice, c->pk_stream));
   CRH_HIP(hipMemsetAsync(c->d_fit_rec, 0, sizeof(uint32_t) * kFitRec * nO, c->pk_stream));
-  launch_fit_extents(c->pk_stream, c->grid, c->d_fit_verts, c->fit_n, (const FitObject*)c->d_fit_objs, nO, S.F, c->d_fit_rec);
+  launch_fit_extents(c->pk_stream, c->grid, c->d_fit_verts, c->fit_n, c->d_fit_objs.as<const FitObject>(), nO, S.F, c->d_fit_rec);
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipMemcpyAsync(rec.data(), c->d_fit_rec, sizeof(uint32_t) * kFitRec * nO, hipMemcpyDeviceToHost, c->pk_stream));
   CRH_HIP(hipStreamSynchronize(c->pk_stream));

@@ -27,23 +27,10 @@ int ensure_ids(crh_ctx* c)
   int rc = pick_stream(c); if (rc) return rc;
   if ((rc = wait_overlay_readers(c))) return rc;
   const size_t n_slots = 64 * (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u), n_px = (size_t)W * H;
-  if (n_slots > c->pk_cap_slots) {
-    c->pk_cap_slots = 0;
-    if ((rc = grow(c, c->d_pk_rays, 32 * n_slots)) || (rc = grow(c, c->d_pk_hit_slot, 16 * n_slots))) return rc;
-    c->pk_cap_slots = n_slots;
-  }
-  if (n_px > c->pk_cap_px) {
-    c->pk_cap_px = 0;
-    if ((rc = grow(c, c->d_pk_hit, 16 * n_px)) || (rc = grow(c, c->d_pk_obj, 4 * n_px))) return rc;
-    c->pk_cap_px = n_px;
-  }
+  CRH_HIP(c->d_pk_rays.reserve(2 * n_slots)); CRH_HIP(c->d_pk_hit_slot.reserve(n_slots));      // (what read the old blocks has been waited for: this stream runs
+  CRH_HIP(c->d_pk_hit.reserve(n_px)); CRH_HIP(c->d_pk_obj.reserve(n_px));                       //  synchronously, the overlay's readers just above)
   if (c->pk_tri_obj_dirty && !c->tri_obj.empty()) {
-    if (c->tri_obj.size() > c->pk_tri_obj_cap) {
-      c->pk_tri_obj_cap = 0;
-      const size_t cap = c->tri_obj.size() + c->tri_obj.size() / 4;      // crh_add_object grows it a little at a time
-      if ((rc = grow(c, c->d_pk_tri_obj, sizeof(int32_t) * cap))) return rc;
-      c->pk_tri_obj_cap = cap;
-    }
+    CRH_HIP(c->d_pk_tri_obj.reserve(c->tri_obj.size(), c->tri_obj.size() / 4));      // crh_add_object grows it a little at a time
     CRH_HIP(hipMemcpyAsync(c->d_pk_tri_obj, c->tri_obj.data(), sizeof(int32_t) * c->tri_obj.size(), hipMemcpyHostToDevice, c->pk_stream));
   }
   c->pk_tri_obj_dirty = false;
@@ -67,8 +54,8 @@ int pick_stream(crh_ctx* c)
   if (c->pk_stream) return CRH_OK;
   CRH_HIP(hipStreamCreateWithFlags(&c->pk_stream, hipStreamNonBlocking));
   CRH_HIP(hipEventCreateWithFlags(&c->pk_fork, hipEventDisableTiming));
-  CRH_HIP(hipMalloc((void**)&c->d_pk_cursor, 64));
-  CRH_HIP(hipMalloc((void**)&c->d_pk_counters, sizeof(DCounters)));
+  CRH_HIP(c->d_pk_cursor.reserve(16));
+  CRH_HIP(c->d_pk_counters.reserve(1));
   CRH_HIP(hipMemsetAsync(c->d_pk_counters, 0, sizeof(DCounters), c->pk_stream));
   return CRH_OK;
 }
@@ -91,14 +78,6 @@ int wait_overlay_readers(crh_ctx* c)
 
 void clear_selection(crh_ctx* c) { c->sel.clear(); c->sel_any = false; c->sel_dirty = false; c->hover = -1; }
 
-void release_pick(crh_ctx* c)
-{
-  if (c->pk_stream) { hipStreamSynchronize(c->pk_stream); hipStreamDestroy(c->pk_stream); }
-  if (c->pk_fork) hipEventDestroy(c->pk_fork);
-  for (void* p : {(void*)c->d_pk_rays, (void*)c->d_pk_hit_slot, (void*)c->d_pk_hit, (void*)c->d_pk_obj, (void*)c->d_pk_tri_obj, (void*)c->d_pk_cursor, (void*)c->d_pk_counters, (void*)c->d_sel})
-    if (p) hipFree(p);
-}
-
 // Called by the LDR read-outs right after the tone map (which includes the ShowSamplingTiles outline: the overlay comes LAST), on the stream the tone map ran on.
 // No selection and no hover: nothing is launched and nothing is computed -- the bytes are the tone map's.
 int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr)
@@ -108,7 +87,7 @@ int overlay_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr)
   int rc = ensure_ids(c); if (rc) return rc;
   if (c->sel_any && c->sel_dirty) {
     if ((rc = wait_overlay_readers(c))) return rc;
-    if (c->sel.size() > c->sel_cap) { c->sel_cap = 0; if ((rc = grow(c, c->d_sel, c->sel.size() + 64))) return rc; c->sel_cap = c->sel.size() + 64; }
+    CRH_HIP(c->d_sel.reserve(c->sel.size(), 64));
     CRH_HIP(hipMemcpyAsync(c->d_sel, c->sel.data(), c->sel.size(), hipMemcpyHostToDevice, c->pk_stream));
     CRH_HIP(hipStreamSynchronize(c->pk_stream));
     c->sel_dirty = false;
@@ -132,10 +111,9 @@ int crh_camera_rays(crh_ctx* c, const uint32_t* xy, uint32_t n, float* rays_out)
   if (!n) return CRH_OK;
   CRH_HIP(hipSetDevice(c->device));
   int rc = pick_stream(c); if (rc) return rc;
-  uint32_t* d_xy = nullptr; float4* d_rays = nullptr;
-  hipError_t e = hipMalloc((void**)&d_xy, 8 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_rays, 32 * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_xy, xy, 8 * (size_t)n, hipMemcpyHostToDevice, c->pk_stream);
+  DevBuf<uint32_t> d_xy; DevBuf<float4> d_rays;       // this call's own: released when it returns
+  CRH_HIP(d_xy.reserve(2 * (size_t)n)); CRH_HIP(d_rays.reserve(2 * (size_t)n));
+  hipError_t e = hipMemcpyAsync(d_xy, xy, 8 * (size_t)n, hipMemcpyHostToDevice, c->pk_stream);
   if (e == hipSuccess) {
     DScene S; fill_scene(c, S);
     Launch L{c->pk_stream, c->grid, false};
@@ -143,9 +121,7 @@ int crh_camera_rays(crh_ctx* c, const uint32_t* xy, uint32_t n, float* rays_out)
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(rays_out, d_rays, 32 * (size_t)n, hipMemcpyDeviceToHost, c->pk_stream);
-  const hipError_t e2 = hipStreamSynchronize(c->pk_stream);
-  if (d_xy) hipFree(d_xy);
-  if (d_rays) hipFree(d_rays);
+  const hipError_t e2 = hipStreamSynchronize(c->pk_stream);      // whatever went wrong: nothing still uses the two blocks when they go
   CRH_HIP(e); CRH_HIP(e2);
   return CRH_OK;
 }

@@ -35,7 +35,7 @@ static int ensure_meter_blocks(crh_ctx* c)
 {
   if (c->d_meter) return CRH_OK;
   CRH_HIP(hipSetDevice(c->device));
-  CRH_HIP(hipMalloc((void**)&c->d_meter, 4 * sizeof(DMeter)));
+  CRH_HIP(c->d_meter.reserve(4));
   return CRH_OK;
 }
 
@@ -47,9 +47,9 @@ int crh_read_hdr(crh_ctx* c, float* out)
   if (!c || !out || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator / null output");
   CRH_HIP(hipSetDevice(c->device));
   const uint32_t n = c->par.width * c->par.height;
-  int rc = ensure_scratch(c, sizeof(float) * 3 * (size_t)n); if (rc) return rc;
+  CRH_HIP(c->d_scratch.reserve(sizeof(float) * 3 * (size_t)n));
   Launch L{cstream(c), c->grid, false};
-  launch_hdr(L, c->assembled_valid ? c->d_assembled : c->d_accum, (float*)c->d_scratch, n);
+  launch_hdr(L, c->assembled_valid ? c->d_assembled : c->d_accum, c->d_scratch.as<float>(), n);
   CRH_HIP(hipMemcpyAsync(out, c->d_scratch, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
@@ -62,13 +62,13 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   CRH_HIP(hipSetDevice(c->device));
   const uint32_t n = c->par.width * c->par.height;
   const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
-  const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked && c->tile_stat_cap >= n_tiles;
-  int rc = ensure_scratch(c, 3 * (size_t)n); if (rc) return rc;
+  const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
+  CRH_HIP(c->d_scratch.reserve(3 * (size_t)n));
   const uint8_t* d_mask = overlay ? c->d_picked : nullptr;            // written by the device-side tile draw of the last iteration
   Launch L{cstream(c), c->grid, false};
   const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
-  launch_tonemap(L, src, (uint8_t*)c->d_scratch, n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, meter_in_front(c, L, src, 0));
-  if ((rc = overlay_ldr(c, L.stream, (uint8_t*)c->d_scratch))) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
+  launch_tonemap(L, src, c->d_scratch.as<uint8_t>(), n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, meter_in_front(c, L, src, 0));
+  if (int rc = overlay_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
   CRH_HIP(hipMemcpyAsync(out, c->d_scratch, 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
@@ -89,12 +89,11 @@ static int read_begin(crh_ctx* c, bool hdr)
     CRH_HIP(hipEventCreateWithFlags(&c->rb_fork, hipEventDisableTiming));
     for (int k = 0; k < 2; ++k) { CRH_HIP(hipEventCreateWithFlags(&c->rb_tm[k], hipEventDisableTiming)); CRH_HIP(hipEventCreateWithFlags(&c->rb_done[k], hipEventDisableTiming)); }
   }
-  if (bytes > c->rb_cap) {
+  if (bytes > c->d_rb[0].cap() || bytes > c->h_rb[0].cap() || bytes > c->d_rb[1].cap() || bytes > c->h_rb[1].cap()) {
     CRH_HIP(hipStreamSynchronize(c->rb_stream));
     if (c->rb_outstanding) return fail(c, CRH_E_INVALID, "the read-back buffers must grow while a read-back is in flight (crh_read_*_end first)");
-    for (int k = 0; k < 2; ++k) { if (c->d_rb[k]) CRH_HIP(hipFree(c->d_rb[k])); if (c->h_rb[k]) CRH_HIP(hipHostFree(c->h_rb[k])); c->d_rb[k] = nullptr; c->h_rb[k] = nullptr; }
-    for (int k = 0; k < 2; ++k) { CRH_HIP(hipMalloc((void**)&c->d_rb[k], bytes)); CRH_HIP(hipHostMalloc((void**)&c->h_rb[k], bytes, hipHostMallocDefault)); }
-    c->rb_cap = bytes;
+    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].release()); CRH_HIP(c->h_rb[k].release()); }
+    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].reserve(bytes)); CRH_HIP(c->h_rb[k].reserve(bytes)); }
   }
   const uint32_t slot = c->rb_head & 1u;
   // everything submitted so far comes first: the frames in flight on the pipeline streams (not joined, they stay in flight) and
@@ -104,10 +103,10 @@ static int read_begin(crh_ctx* c, bool hdr)
   CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->rb_fork, 0));
   Launch L{c->rb_stream, c->grid, false};
   const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
-  if (hdr) launch_hdr(L, src, (float*)c->d_rb[slot], n);
+  if (hdr) launch_hdr(L, src, c->d_rb[slot].as<float>(), n);
   else {
     const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
-    const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked && c->tile_stat_cap >= n_tiles;
+    const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
     launch_tonemap(L, src, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, meter_in_front(c, L, src, 1 + (int)slot));
     if (int rc = overlay_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // hover / selection (crh_pick.cpp)
   }

@@ -79,9 +79,8 @@ int reduce_impl(crh_ctx* const* ctxs, uint32_t n, uint32_t root, bool fake_devic
   }
   CRH_HIP(hipSetDevice(c->device));
   if (!c->d_assembled || c->assembledW != W || c->assembledH != H) {
-    if (c->d_assembled) { CRH_HIP(hipFree(c->d_assembled)); c->d_assembled = nullptr; }
-    if (c->d_peer_stage) { CRH_HIP(hipFree(c->d_peer_stage)); c->d_peer_stage = nullptr; }
-    CRH_HIP(hipMalloc((void**)&c->d_assembled, sizeof(float4) * n4));
+    CRH_HIP(c->d_assembled.release()); CRH_HIP(c->d_peer_stage.release());      // another size: blocks of exactly that size, a smaller one too
+    CRH_HIP(c->d_assembled.reserve(n4));
     c->assembledW = W; c->assembledH = H;
   }
   // every shard's queued rendering must have landed before its accumulator is read by another stream / device
@@ -144,7 +143,7 @@ int reduce_impl(crh_ctx* const* ctxs, uint32_t n, uint32_t root, bool fake_devic
       if (i == root) continue;
       const float4* src = ctxs[i]->d_accum;
       if (ctxs[i]->device != c->device) {
-        if (!c->d_peer_stage) CRH_HIP(hipMalloc((void**)&c->d_peer_stage, sizeof(float4) * n4));
+        CRH_HIP(c->d_peer_stage.reserve(n4));
         CRH_HIP(hipMemcpyPeerAsync(c->d_peer_stage, c->device, ctxs[i]->d_accum, ctxs[i]->device, sizeof(float4) * n4, cstream(c)));
         src = c->d_peer_stage;
       }

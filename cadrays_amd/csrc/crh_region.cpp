@@ -64,18 +64,6 @@ void records_to_stats(const uint32_t* rec, uint32_t n_records, crh_region_stats*
 
 }  // namespace
 
-namespace crh {
-namespace api {
-
-void release_region(crh_ctx* c)
-{
-  for (void* p : {c->d_rg_edges, (void*)c->d_rg_rec}) if (p) hipFree(p);
-  c->d_rg_edges = nullptr; c->d_rg_rec = nullptr; c->rg_rec_cap = 0;
-}
-
-}  // namespace api
-}  // namespace crh
-
 extern "C" {
 
 int crh_query_region(crh_ctx* c, const uint32_t rect[4], const int32_t* poly_xy, uint32_t n_poly, crh_region_stats* out, uint32_t n_objects)
@@ -90,19 +78,14 @@ int crh_query_region(crh_ctx* c, const uint32_t rect[4], const int32_t* poly_xy,
   CRH_HIP(hipSetDevice(c->device));
   if ((rc = pick_stream(c))) return rc;
   const size_t n_rec = (size_t)nO + 1;
-  if (!c->d_rg_edges) { if ((rc = grow(c, c->d_rg_edges, sizeof(RegionEdge) * kRegionMaxEdges))) return rc; }
-  if (n_rec > c->rg_rec_cap) {
-    c->rg_rec_cap = 0;
-    const size_t cap = n_rec + 16;                       // crh_add_object grows the scene one object at a time
-    if ((rc = grow(c, c->d_rg_rec, sizeof(uint32_t) * kRegionRec * cap))) return rc;
-    c->rg_rec_cap = cap;
-  }
+  CRH_HIP(c->d_rg_edges.reserve(sizeof(RegionEdge) * kRegionMaxEdges));
+  CRH_HIP(c->d_rg_rec.reserve((size_t)kRegionRec * n_rec, (size_t)kRegionRec * 16));      // crh_add_object grows the scene one object at a time
   std::vector<uint32_t> rec((size_t)kRegionRec * n_rec, 0u);
   if (S.n_edges) CRH_HIP(hipMemcpyAsync(c->d_rg_edges, edges.data(), sizeof(RegionEdge) * S.n_edges, hipMemcpyHostToDevice, c->pk_stream));
   CRH_HIP(hipMemsetAsync(c->d_rg_rec, 0, sizeof(uint32_t) * kRegionRec * n_rec, c->pk_stream));
   // ONE workgroup per compute unit: every workgroup ends with its atomics on the records, and fewer, longer-running workgroups were faster in every form measured
   // (4 / 2 / 1 per compute unit)
-  launch_region_stats(c->pk_stream, std::max(c->grid / 4, 1), c->d_pk_obj, c->d_pk_hit, (const RegionEdge*)c->d_rg_edges, S, nO, c->d_rg_rec);
+  launch_region_stats(c->pk_stream, std::max(c->grid / 4, 1), c->d_pk_obj, c->d_pk_hit, c->d_rg_edges.as<const RegionEdge>(), S, nO, c->d_rg_rec);
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipMemcpyAsync(rec.data(), c->d_rg_rec, sizeof(uint32_t) * kRegionRec * n_rec, hipMemcpyDeviceToHost, c->pk_stream));
   CRH_HIP(hipStreamSynchronize(c->pk_stream));

@@ -59,9 +59,12 @@ int upload_textures(crh_ctx* c)
     all.insert(all.end(), c->textures[i].rgba.begin(), c->textures[i].rgba.end());
   }
   if (all.empty()) all.assign(4, 0.f);
-  int rc;
-  if ((rc = dev_upload(c, c->d_texels, all.data(), all.size() * sizeof(float)))) return rc;
-  if ((rc = dev_upload(c, c->d_tex_desc, desc.data(), desc.size() * sizeof(uint32_t)))) return rc;
+  CRH_HIP(hipStreamSynchronize(cstream(c)));             // kernels in flight may still read the old texels
+  CRH_HIP(c->d_texels.release()); CRH_HIP(c->d_tex_desc.release());      // blocks of exactly this size, a smaller one too
+  CRH_HIP(c->d_texels.reserve(all.size() / 4)); CRH_HIP(c->d_tex_desc.reserve(desc.size() / 4));
+  CRH_HIP(hipMemcpyAsync(c->d_texels, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, cstream(c)));
+  CRH_HIP(hipMemcpyAsync(c->d_tex_desc, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cstream(c)));
+  CRH_HIP(hipStreamSynchronize(cstream(c)));             // `all` and `desc` are temporaries
   c->textures_dirty = false;
   return CRH_OK;
 }
@@ -84,7 +87,7 @@ int upload_lights(crh_ctx* c)
     }
     o[4] = s.emission[0]; o[5] = s.emission[1]; o[6] = s.emission[2];
   }
-  return dev_put(c, c->d_lights, c->cap_lights, l.data(), l.size() * sizeof(float), 8 * 32);
+  return dev_put(c, c->d_lights, l.data(), l.size() * sizeof(float), 8 * 32);
 }
 
 static bool is_identity(const float* m)
@@ -144,14 +147,14 @@ int build_tlas(crh_ctx* c)
     c->root = troot;
     for (int a = 0; a < 3; ++a) { c->bvh.bbmin[a] = c->tlas_lo[a]; c->bvh.bbmax[a] = c->tlas_hi[a]; }
   }
-  if (!c->d_ibox) CRH_HIP(hipMalloc((void**)&c->d_ibox, sizeof(float4) * kMaxIBox));
+  CRH_HIP(c->d_ibox.reserve(kMaxIBox));
   crh_box_sphere(c->tlas_lo, c->tlas_hi, c->usph);
   if (n <= kMaxIBox) {
     float ib[4 * kMaxIBox] = {0};
     for (uint32_t i = 0; i < n; ++i) crh_box_sphere(&boxes[6 * (size_t)i], &boxes[6 * (size_t)i + 3], &ib[4 * i]);
     int rc_b = stage_copy(c, c->d_ibox, ib, sizeof(float) * 4 * n); if (rc_b) return rc_b;
   }
-  return dev_put(c, c->d_inst, c->cap_inst, table.data(), table.size() * sizeof(float), 32 * sizeof(float) * ((size_t)c->nO + 64));
+  return dev_put(c, c->d_inst, table.data(), table.size() * sizeof(float), 32 * sizeof(float) * ((size_t)c->nO + 64));
 }
 
 // the object-space tree of object ob, appended behind the trees built so far; its triangles take the next leaf positions
@@ -348,12 +351,11 @@ static int apply_objects(crh_ctx* c, const float* xf, const uint8_t* visible)
   }
   if (!ppos.empty()) {
     const size_t nb = ppos.size() * 4, rb = prec.size() * 4, need = ((nb + 255) & ~(size_t)255) + rb;
-    if (need > c->cap_patch) {
+    if (need > c->d_patch.cap()) {
       CRH_HIP(hipStreamSynchronize(cstream(c)));
-      if (c->d_patch) { CRH_HIP(hipFree(c->d_patch)); c->d_patch = nullptr; c->cap_patch = 0; }
-      CRH_HIP(hipMalloc(&c->d_patch, need + need / 2)); c->cap_patch = need + need / 2;
+      CRH_HIP(c->d_patch.reserve(need, need / 2));
     }
-    char* base = (char*)c->d_patch; char* recs = base + ((nb + 255) & ~(size_t)255);
+    char* base = c->d_patch.as<char>(); char* recs = base + ((nb + 255) & ~(size_t)255);
     auto put = [&](void* dst, const void* src, size_t bytes) -> int {
       if (bytes <= (4u << 20)) return stage_copy(c, dst, src, bytes);
       CRH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cstream(c))); CRH_HIP(hipStreamSynchronize(cstream(c))); return CRH_OK;
@@ -367,10 +369,10 @@ static int apply_objects(crh_ctx* c, const float* xf, const uint8_t* visible)
   if ((rc = build_tlas(c))) return rc;
   if (had_instances != !c->inst.empty()) c->feed_tune.restart();      // the frame kernel's other instantiation (one walk / two levels): its feeder count is measured again
   const size_t tail = c->bvh.nodes.size() - old_nodes;
-  if (c->bvh.nodes.size() * sizeof(QNode) > c->cap_nodes) {          // more object trees than crh_build left room for: the whole array again, with head-room
-    if ((rc = dev_put(c, c->d_nodes, c->cap_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(QNode), c->bvh.nodes.size() * sizeof(QNode) / 2 + (size_t)(4 * c->nO + 64) * sizeof(QNode)))) return rc;
+  if (c->bvh.nodes.size() * sizeof(QNode) > c->d_nodes.bytes()) {          // more object trees than crh_build left room for: the whole array again, with head-room
+    if ((rc = dev_put(c, c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(QNode), c->bvh.nodes.size() * sizeof(QNode) / 2 + (size_t)(4 * c->nO + 64) * sizeof(QNode)))) return rc;
   } else if (tail) {
-    const size_t bytes = tail * sizeof(QNode); void* dst = (char*)c->d_nodes + (size_t)old_nodes * sizeof(QNode);
+    const size_t bytes = tail * sizeof(QNode); void* dst = c->d_nodes.as<char>() + (size_t)old_nodes * sizeof(QNode);
     if (bytes <= (4u << 20)) { if ((rc = stage_copy(c, dst, c->bvh.nodes.data() + old_nodes, bytes))) return rc; }
     else { CRH_HIP(hipMemcpyAsync(dst, c->bvh.nodes.data() + old_nodes, bytes, hipMemcpyHostToDevice, cstream(c))); CRH_HIP(hipStreamSynchronize(cstream(c))); }
   }
@@ -397,18 +399,6 @@ int crh_set_visibility(crh_ctx* c, const uint8_t* visible, uint32_t nO)
   return apply_objects(c, nullptr, visible);
 }
 
-// Grow a leaf-ordered device array to `cap` positions, keeping the first `keep`: a new allocation, a device-to-device copy, the old one freed.
-static int grow_positions(crh_ctx* c, float4*& d, size_t rec_float4, size_t keep, size_t cap)
-{
-  float4* n = nullptr;
-  CRH_HIP(hipMalloc((void**)&n, cap * rec_float4 * sizeof(float4)));
-  if (d && keep) CRH_HIP(hipMemcpyAsync(n, d, keep * rec_float4 * sizeof(float4), hipMemcpyDeviceToDevice, cstream(c)));
-  CRH_HIP(hipStreamSynchronize(cstream(c)));
-  if (d) CRH_HIP(hipFree(d));
-  d = n;
-  return CRH_OK;
-}
-
 int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* uv, uint32_t nV, const int32_t* tri, uint32_t nT,
                    const float* xform, uint32_t* object_out)
 {
@@ -432,13 +422,18 @@ int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* 
   if ((uint64_t)c->n_pos + reserved + nT >= (1ull << 28)) return fail(c, CRH_E_INVALID, "too many triangles (limit 2^28)");
   if ((size_t)c->n_pos + reserved + nT > c->cap_pos) {
     const size_t cap = (size_t)c->n_pos + (size_t)reserved + 2 * (size_t)nT + c->cap_pos / 4;
-    int rc;
     CRH_HIP(hipStreamSynchronize(cstream(c)));
     for (int k = 0; k < 8; ++k) if (c->pipe.pipe_pending[k]) CRH_HIP(hipEventSynchronize(c->lane_join[k]));      // frames in flight still read the old arrays
-    if ((rc = grow_positions(c, c->d_tris, kTriStride, c->n_pos, cap))) return rc;
-    if ((rc = grow_positions(c, c->d_shade, 4, c->n_pos, cap))) return rc;
-    if (c->d_uvs && (rc = grow_positions(c, c->d_uvs, 2, c->n_pos, cap))) return rc;
-    if ((rc = grow_positions(c, c->d_verts, 3, c->n_pos, cap))) return rc;
+    // a new block, the positions in use copied over device-to-device and waited for, the old block released; refused: that array keeps what it has, and the
+    // scene stays renderable with the old number of positions (cap_pos moves only when all four have room)
+    auto keep = [c](float4* to, const float4* from, size_t n4) {
+      hipError_t e = hipMemcpyAsync(to, from, n4 * sizeof(float4), hipMemcpyDeviceToDevice, cstream(c));
+      return e != hipSuccess ? e : hipStreamSynchronize(cstream(c));
+    };
+    CRH_HIP(c->d_tris.reserve_keep(cap * kTriStride, (size_t)c->n_pos * kTriStride, keep));
+    CRH_HIP(c->d_shade.reserve_keep(cap * 4, (size_t)c->n_pos * 4, keep));
+    if (c->d_uvs) CRH_HIP(c->d_uvs.reserve_keep(cap * 2, (size_t)c->n_pos * 2, keep));
+    CRH_HIP(c->d_verts.reserve_keep(cap * 3, (size_t)c->n_pos * 3, keep));
     c->cap_pos = cap;
   }
   // host arrays: the new object's vertices and triangles behind the scene's own (vertex indices shifted), one more object
@@ -475,7 +470,7 @@ int crh_set_materials(crh_ctx* c, const crh_bsdf* m, uint32_t n)
   if (!all_finite((const float*)m, 32 * (size_t)n)) return fail(c, CRH_E_INVALID, "material holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
   c->mats.assign(m, m + n); c->pending_n = 0;
-  return dev_put(c, c->d_mats, c->cap_mats, c->mats.data(), sizeof(crh_bsdf) * n, 16 * sizeof(crh_bsdf));
+  return dev_put(c, c->d_mats, c->mats.data(), sizeof(crh_bsdf) * n, 16 * sizeof(crh_bsdf));
 }
 
 int crh_set_lights(crh_ctx* c, const crh_light* l, uint32_t n)
@@ -496,7 +491,7 @@ int crh_set_envmap(crh_ctx* c, const float* rgb, uint32_t w, uint32_t h)
   if (rgb && w && h) {
     std::vector<float> t(4 * (size_t)w * h);
     for (size_t i = 0; i < (size_t)w * h; ++i) { t[4 * i] = rgb[3 * i]; t[4 * i + 1] = rgb[3 * i + 1]; t[4 * i + 2] = rgb[3 * i + 2]; t[4 * i + 3] = 0.f; }
-    int rc = dev_put(c, c->d_env, c->cap_env, t.data(), t.size() * sizeof(float)); if (rc) return rc;
+    int rc = dev_put(c, c->d_env, t.data(), t.size() * sizeof(float)); if (rc) return rc;
     c->envW = w; c->envH = h;
   }
   return CRH_OK;      // without a map the kernels take the background colour (fill_scene hands them a null pointer); the allocation is kept
@@ -655,9 +650,8 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
     // room for the instance table of ANY later placement (one record per object + one per instance), so that the first crh_set_transforms --
     // the user has just grabbed the gizmo -- allocates nothing
     const size_t want_inst = 128 * (2 * (size_t)c->nO + 64);
-    if (c->cap_inst < want_inst) {
-      if (c->d_inst) { CRH_HIP(hipFree(c->d_inst)); c->d_inst = nullptr; c->cap_inst = 0; }
-      CRH_HIP(hipMalloc((void**)&c->d_inst, want_inst)); c->cap_inst = want_inst;
+    if (c->d_inst.bytes() < want_inst) {
+      CRH_HIP(c->d_inst.reserve(want_inst / sizeof(float4)));
       CRH_HIP(hipMemsetAsync(c->d_inst, 0, want_inst, cstream(c)));
     }
   }
@@ -668,40 +662,42 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
   c->h_tris.clear();
   fill_records(c, 0, c->n_pos, tr, sh, uvr, c->two_level ? &vt : nullptr);
   phase("leaf-ordered records");
-  c->cap_pos = (size_t)std::max(c->n_pos, 1u) + (c->two_level ? c->n_static : 0u);
+  const size_t cap_pos = (size_t)std::max(c->n_pos, 1u) + (c->two_level ? c->n_static : 0u);
+  c->cap_pos = 0;                                        // in force again once every leaf-ordered array below has that room
   if (c->two_level) {
     // host arrays that grow when an object tree is built later: reserve now -- the first growth of a 33 MB node vector or a 48 MB record vector is a
     // reallocation + copy of 10-20 ms, which used to land in the first dragged frame
     c->bvh.nodes.reserve(c->bvh.nodes.size() + 2 * (size_t)c->n_static + 4 * (size_t)c->nO + 64);
-    c->h_tris.reserve(12 * c->cap_pos); c->bvh.prim_order.reserve(c->cap_pos); c->pos_obj.reserve(c->cap_pos);
+    c->h_tris.reserve(12 * cap_pos); c->bvh.prim_order.reserve(cap_pos); c->pos_obj.reserve(cap_pos);
   }
   int rc;
   // head-room behind the node array: object trees built later by crh_set_transforms (<= ~1.5 nodes per triangle incl. alignment holes) and the top-level tree
-  if ((rc = dev_put(c, c->d_nodes, c->cap_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(QNode),
+  if ((rc = dev_put(c, c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(QNode),
                     (size_t)((c->two_level ? 2 * (size_t)c->n_static : 0) + 4 * (size_t)c->nO + 64) * sizeof(QNode)))) return rc;
-  auto alloc_put = [&](float4*& dptr, const std::vector<float>& v, size_t rec_floats) -> int {
+  auto alloc_put = [&](DevBuf<float4>& d, const std::vector<float>& v, size_t rec_floats) -> int {      // a block of exactly cap_pos records, a smaller one too
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    if (dptr) { CRH_HIP(hipFree(dptr)); dptr = nullptr; }
-    CRH_HIP(hipMalloc((void**)&dptr, c->cap_pos * rec_floats * sizeof(float)));
-    CRH_HIP(hipMemcpyAsync(dptr, v.data(), (size_t)std::max(c->n_pos, 1u) * rec_floats * sizeof(float), hipMemcpyHostToDevice, cstream(c)));
+    CRH_HIP(d.release());
+    CRH_HIP(d.reserve(cap_pos * rec_floats / 4));
+    CRH_HIP(hipMemcpyAsync(d, v.data(), (size_t)std::max(c->n_pos, 1u) * rec_floats * sizeof(float), hipMemcpyHostToDevice, cstream(c)));
     CRH_HIP(hipStreamSynchronize(cstream(c)));
     return CRH_OK;
   };
   if ((rc = alloc_put(c->d_tris, tr, 4 * kTriStride))) return rc;
   if ((rc = alloc_put(c->d_shade, sh, 16))) return rc;
   if (!c->uv.empty()) { if ((rc = alloc_put(c->d_uvs, uvr, 8))) return rc; }
-  else if (c->d_uvs) { CRH_HIP(hipFree(c->d_uvs)); c->d_uvs = nullptr; }
+  else CRH_HIP(c->d_uvs.release());
   if (c->two_level) { if ((rc = alloc_put(c->d_verts, vt, 12))) return rc; }
-  else if (c->d_verts) { CRH_HIP(hipFree(c->d_verts)); c->d_verts = nullptr; }
+  else CRH_HIP(c->d_verts.release());
+  c->cap_pos = cap_pos;
   // packet nodes for the camera rays of wide batches (k_trace_packets<true>): the node array again with its quantised planes as floats, 128 B per node.
   // Single-level scenes only (a scene with objects grows its node array while the user drags; its packets read the 64-B nodes)
   if (!c->two_level && c->packets > 0) {
     const size_t nn = c->bvh.nodes.size();
-    if (nn > c->cap_pnodes) { if (c->d_pnodes) { CRH_HIP(hipFree(c->d_pnodes)); c->d_pnodes = nullptr; c->cap_pnodes = 0; } CRH_HIP(hipMalloc((void**)&c->d_pnodes, nn * 128)); c->cap_pnodes = nn; }
+    CRH_HIP(c->d_pnodes.reserve(nn * 8));
     Launch Lx{cstream(c), 64, false};
     launch_expand_packet_nodes(Lx, c->d_nodes, c->d_pnodes, (uint32_t)nn);
     CRH_HIP(hipGetLastError());
-  } else if (c->d_pnodes) { CRH_HIP(hipFree(c->d_pnodes)); c->d_pnodes = nullptr; c->cap_pnodes = 0; }
+  } else CRH_HIP(c->d_pnodes.release());
   phase("upload");
   if (c->two_level) {
     // what the FIRST crh_set_transforms would otherwise allocate while the user is dragging: the staging of the triangle patches of the largest object
@@ -710,16 +706,12 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
     // milliseconds each would otherwise land in the first dragged frame)
     const size_t want_stage = std::min<size_t>(4u << 20, (size_t)biggest * 64 + (size_t)c->nO * 160 + 65536);
     for (BuiltScene::Stage& st : c->stage)
-      if (st.cap < want_stage) {
+      if (st.p.cap() < want_stage) {
         if (st.used) CRH_HIP(hipEventSynchronize(st.ev));
-        if (st.p) { CRH_HIP(hipHostFree(st.p)); st.p = nullptr; st.cap = 0; }
-        CRH_HIP(hipHostMalloc(&st.p, want_stage, hipHostMallocDefault)); st.cap = want_stage;
+        CRH_HIP(st.p.reserve(want_stage));
       }
     const size_t want_patch = 2 * ((size_t)biggest * 52 + 512);
-    if (c->cap_patch < want_patch) {
-      if (c->d_patch) { CRH_HIP(hipFree(c->d_patch)); c->d_patch = nullptr; c->cap_patch = 0; }
-      CRH_HIP(hipMalloc(&c->d_patch, want_patch)); c->cap_patch = want_patch;
-    }
+    CRH_HIP(c->d_patch.reserve(want_patch));
   }
   c->built = true; c->feed_tune.restart(); c->tile_order.remeasure();
   if (c->two_level && c->inst.empty()) {
@@ -735,7 +727,7 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
       S.split = 1; launch_trace_nearest(LT, S, c->paths, c->queues, 0, 0, c->d_counters); launch_trace_any(LT, S, c->paths, c->queues, c->d_counters);      // and the second-pass ones
     }
     Launch L{cstream(c), 64, false};
-    launch_scatter_tris(L, c->d_tris, (const uint32_t*)c->d_patch, (const float4*)c->d_patch, 0);
+    launch_scatter_tris(L, c->d_tris, c->d_patch.as<uint32_t>(), c->d_patch.as<float4>(), 0);
     CRH_HIP(hipGetLastError());
   }
   if (c->two_level && !c->hidden.empty()) { if (c->hidden.size() != c->nO) c->hidden.assign(c->nO, 0); if ((rc = apply_objects(c, nullptr, nullptr))) return rc; }      // objects erased before the build: baked like the rest, then disabled

@@ -96,7 +96,7 @@ int ensure_lanes(crh_ctx* c)
     CRH_HIP(hipEventCreateWithFlags(&c->lane_join[k], hipEventDisableTiming));
   }
   CRH_HIP(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
-  CRH_HIP(hipMalloc((void**)&c->d_lane_counts, kCounts * sizeof(uint32_t) * 8));
+  CRH_HIP(c->d_lane_counts.reserve(kCounts * 8));
   CRH_HIP(hipMemsetAsync(c->d_lane_counts, 0, kCounts * sizeof(uint32_t) * 8, cstream(c)));
   return CRH_OK;
 }
@@ -156,15 +156,15 @@ int validate_tiles(crh_ctx* c, const uint32_t* tiles, uint32_t nt)
 // one (an unchanged tile list is not sent again).  d_list: where this call's list sits.
 int resident_tile_list(crh_ctx* c, const uint32_t* tiles, uint32_t nt, uint32_t*& d_list)
 {
-  if (nt > c->tile_cap) c->h_tile_ids.clear();
-  int rc = grow_u32(c, c->d_tile_ids, c->tile_cap, nt); if (rc) return rc;
+  if (nt > c->d_tile_ids.cap()) c->h_tile_ids.clear();
+  int rc = grow_u32(c, c->d_tile_ids, nt); if (rc) return rc;
   // Round 6: TWO lists stay on the device -- crh_render hands over the image's tiles either row-major or most-expensive-first (crh_context.h TileOrder), by what
   // is in flight; switching between two resident lists costs nothing, and a frame in flight keeps reading the one it was launched with.  A third list replaces the
   // one the previous call did not use (through the context's stream: behind every frame that still reads it).
   if (c->h_tile_ids.size() == nt && std::memcmp(c->h_tile_ids.data(), tiles, sizeof(uint32_t) * nt) == 0) { d_list = c->d_tile_ids; c->tile_list_last = 0; }
   else if (c->h_tile_ids2.size() == nt && std::memcmp(c->h_tile_ids2.data(), tiles, sizeof(uint32_t) * nt) == 0) { d_list = c->d_tile_ids2; c->tile_list_last = 1; }
   else if (c->tile_list_last == 0 && !c->h_tile_ids.empty()) {      // the first list is the one in use: the new one goes to the second
-    if ((rc = grow_u32(c, c->d_tile_ids2, c->tile_cap2, nt))) return rc;
+    if ((rc = grow_u32(c, c->d_tile_ids2, nt))) return rc;
     if ((rc = stage_copy(c, c->d_tile_ids2, tiles, sizeof(uint32_t) * nt))) return rc;
     c->h_tile_ids2.assign(tiles, tiles + nt); d_list = c->d_tile_ids2; c->tile_list_last = 1;
   } else {
@@ -197,10 +197,10 @@ int tile_cost_sums(crh_ctx* c, Lane& ln)
   const uint32_t all_tiles = plan::tile_count(c->par.width, c->par.height, c->par.tile_size);
   if (to.n != all_tiles) {
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    if (to.d_cost) CRH_HIP(hipFree(to.d_cost)); if (to.h_cost) CRH_HIP(hipHostFree(to.h_cost));
-    to.d_cost = nullptr; to.h_cost = nullptr;
-    CRH_HIP(hipMalloc((void**)&to.d_cost, sizeof(uint32_t) * all_tiles)); CRH_HIP(hipMemsetAsync(to.d_cost, 0, sizeof(uint32_t) * all_tiles, cstream(c)));      // (never the NULL stream: once it exists every launch on the context's streams pays for it -- the drag loop lost 2.3 % to one hipMemset here)
-    CRH_HIP(hipHostMalloc((void**)&to.h_cost, sizeof(uint32_t) * all_tiles, hipHostMallocDefault));
+    to.n = 0;                                               // (no count is in force until both blocks have the new one)
+    CRH_HIP(to.d_cost.release()); CRH_HIP(to.h_cost.release());      // blocks of exactly this size, a smaller one too
+    CRH_HIP(to.d_cost.reserve(all_tiles)); CRH_HIP(hipMemsetAsync(to.d_cost, 0, sizeof(uint32_t) * all_tiles, cstream(c)));      // (never the NULL stream: once it exists every launch on the context's streams pays for it -- the drag loop lost 2.3 % to one hipMemset here)
+    CRH_HIP(to.h_cost.reserve(all_tiles));
     to.n = all_tiles; to.pending = false; to.dirty = false; to.cls.clear(); to.order.clear();
   }
   if (to.streak >= 2u && to.verdict != 2u) { ln.tile_cost = to.d_cost; to.dirty = true; ++to.frames_collected; }      // (a host that keeps frames in flight gets no new list anyway: nothing is collected for it)
@@ -290,7 +290,7 @@ int render_pipelined_frame(crh_ctx* c, const uint32_t* d_list, uint32_t nt, uint
 // The call as batches of `group` tiles x `spb` samples on the context's stream, one after the other
 int render_batches(crh_ctx* c, const uint32_t* d_list, uint32_t nt, uint32_t first, uint32_t ns, uint32_t group, uint32_t spb)
 {
-  int rc = grow_u32(c, c->d_seeds, c->seed_cap, ns); if (rc) return rc;
+  int rc = grow_u32(c, c->d_seeds, ns); if (rc) return rc;
   {
     std::vector<uint32_t> seeds(ns);
     plan::frame_seeds(c->par.seed, first, ns, seeds.data());
@@ -347,14 +347,11 @@ int render_impl(crh_ctx* c, const uint32_t* tiles, uint32_t nt, uint32_t first, 
 int tile_stats(crh_ctx* c, std::vector<float>& err, std::vector<uint32_t>& cnt)
 {
   const uint32_t nt = plan::tile_count(c->par.width, c->par.height, c->par.tile_size);
-  if (nt > c->tile_stat_cap) {
+  if (nt > c->d_tile_err.cap() || nt > c->d_tile_cnt.cap()) {
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    if (c->d_tile_err) CRH_HIP(hipFree(c->d_tile_err));
-    if (c->d_tile_cnt) CRH_HIP(hipFree(c->d_tile_cnt));
-    for (void* q : {(void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) CRH_HIP(hipFree(q));
-    c->d_tile_cdf = nullptr; c->d_picked = nullptr; c->d_adapt_n = nullptr; c->picked_valid = false;      // the sampler allocates them again at this size
-    CRH_HIP(hipMalloc((void**)&c->d_tile_err, sizeof(float) * nt)); CRH_HIP(hipMalloc((void**)&c->d_tile_cnt, sizeof(uint32_t) * nt));
-    c->tile_stat_cap = nt;
+    c->picked_valid = false;                                // the sampler allocates its three again at this size
+    CRH_HIP(c->d_tile_cdf.release()); CRH_HIP(c->d_picked.release()); CRH_HIP(c->d_adapt_n.release());
+    CRH_HIP(c->d_tile_err.reserve(nt)); CRH_HIP(c->d_tile_cnt.reserve(nt));
   }
   DScene S; fill_scene(c, S);
   Launch L{cstream(c), c->grid, false};
@@ -377,16 +374,13 @@ int adaptive_iteration(crh_ctx* c)
   const uint32_t ts = c->par.tile_size, tpp = ts * ts;
   const uint32_t nt = plan::tile_count(c->par.width, c->par.height, ts);
   const uint32_t most = std::min(c->adaptive_tiles, nt);                // distinct tiles one iteration can draw
-  if (nt > c->tile_stat_cap || !c->d_tile_cdf) {
+  if (nt > c->d_tile_err.cap() || nt > c->d_tile_cnt.cap() || nt > c->d_tile_cdf.cap() || nt > c->d_picked.cap() || !c->d_adapt_n) {
     CRH_HIP(hipStreamSynchronize(cstream(c)));
-    for (void* q : {(void*)c->d_tile_err, (void*)c->d_tile_cnt, (void*)c->d_tile_cdf, (void*)c->d_picked, (void*)c->d_adapt_n}) if (q) CRH_HIP(hipFree(q));
-    c->d_tile_err = nullptr; c->d_tile_cnt = nullptr; c->d_tile_cdf = nullptr; c->d_picked = nullptr; c->d_adapt_n = nullptr; c->tile_stat_cap = 0;
-    CRH_HIP(hipMalloc((void**)&c->d_tile_err, sizeof(float) * nt)); CRH_HIP(hipMalloc((void**)&c->d_tile_cnt, sizeof(uint32_t) * nt));
-    CRH_HIP(hipMalloc((void**)&c->d_tile_cdf, sizeof(float) * nt)); CRH_HIP(hipMalloc((void**)&c->d_picked, nt)); CRH_HIP(hipMalloc((void**)&c->d_adapt_n, 64));
-    c->tile_stat_cap = std::max(nt, c->tile_stat_cap);
+    CRH_HIP(c->d_tile_err.reserve(nt)); CRH_HIP(c->d_tile_cnt.reserve(nt));
+    CRH_HIP(c->d_tile_cdf.reserve(nt)); CRH_HIP(c->d_picked.reserve(nt)); CRH_HIP(c->d_adapt_n.reserve(16));
   }
-  if ((rc = grow_u32(c, c->d_tile_ids, c->tile_cap, most))) return rc;
-  if ((rc = grow_u32(c, c->d_seeds, c->seed_cap, most))) return rc;
+  if ((rc = grow_u32(c, c->d_tile_ids, most))) return rc;
+  if ((rc = grow_u32(c, c->d_seeds, most))) return rc;
   c->h_tile_ids.clear();                                                // the device is about to write its own list there
   rc = ensure_paths(c, most * tpp); if (rc) return rc;
   DScene S; fill_scene(c, S);
@@ -438,8 +432,8 @@ int render_lookahead(crh_ctx* c, const std::vector<uint32_t>& all, uint32_t n, b
         }
       }
       int rc = upload_textures(c); if (rc) return rc;
-      if ((rc = grow_u32(c, c->d_tile_ids, c->tile_cap, nt))) return rc;
-      if ((rc = grow_u32(c, c->d_seeds, c->seed_cap, k))) return rc;
+      if ((rc = grow_u32(c, c->d_tile_ids, nt))) return rc;
+      if ((rc = grow_u32(c, c->d_seeds, k))) return rc;
       std::vector<uint32_t> seeds(k);
       plan::frame_seeds(c->par.seed, c->frames_done, k, seeds.data());
       c->h_tile_ids.clear();

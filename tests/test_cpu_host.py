@@ -238,3 +238,27 @@ def test_every_environment_variable_the_library_reads_is_in_its_table(hip_lib):
     assert read == set(table), (sorted(read - set(table)), sorted(set(table) - read))
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert all(name in doc for name in table), [n for n in table if n not in doc]
+
+
+def test_only_the_two_memory_policies_call_the_hip_allocator():
+    """Device and pinned memory have ONE owner type (csrc/crh_devmem.h); hipMalloc / hipFree / hipHostMalloc / hipHostFree are called by its two memory
+    policies in crh_context.h and nowhere else in the library's sources -- crh_destroy frees no pointer by hand."""
+    import glob
+    import re
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\(")
+    found = {}
+    for f in sorted(glob.glob(os.path.join(ROOT, "cadrays_amd", "csrc", "*"))):
+        if f.endswith((".cpp", ".hip", ".h")):
+            text = open(f).read()
+            if os.path.basename(f) == "crh_context.h":
+                policies = re.findall(r"^struct (?:DeviceMem|PinnedMem) \{\n(?:.*\n)*?\};\n", text, re.M)
+                assert len(policies) == 2, policies
+                assert sorted(calls.findall("".join(policies))) == ["hipFree", "hipHostFree", "hipHostMalloc", "hipMalloc"]
+                for p in policies:
+                    text = text.replace(p, "")
+            if calls.search(text):
+                found[os.path.basename(f)] = calls.findall(text)
+    assert not found, found
+    ctx = open(os.path.join(ROOT, "cadrays_amd", "csrc", "crh_context.cpp")).read()
+    destroy = re.search(r"^void crh_destroy\(crh_ctx\* c\)\n\{\n(?:.*\n)*?\}\n", ctx, re.M)
+    assert destroy and "delete c;" in destroy.group(0) and not calls.search(destroy.group(0)), destroy
