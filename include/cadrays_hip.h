@@ -67,7 +67,14 @@ typedef struct crh_bsdf {
 /* V3d directional / positional light as the light editor sets it
  * (LightSourcesEditor.cxx:242-310): colour*intensity -> emission;
  * directional: vec = direction the light travels, smoothness = cone half-angle [rad];
- * positional : vec = position, smoothness = sphere radius. */
+ * positional : vec = position, smoothness = sphere radius.
+ * What a ray SEES of them (a camera ray, or a bounce that leaves the scene):
+ * directional: the emission, when the ray's direction lies within `smoothness` radians of the direction towards the light (-vec) and the ray hits
+ *   nothing; overlapping cones add; smoothness 0 is a delta light and is never seen.
+ * positional : the emission, when the ray's direction lies within the cone of half-angle atan(r / d) around the direction to the centre, d = the distance
+ *   from the ray's ORIGIN to the centre, and d is smaller than the distance to the ray's hit (the nearest such light wins and replaces the hit; r = 0 is
+ *   never seen).  This is the disc of radius r through the centre that faces the origin, not the sphere, whose outline has the half-angle asin(r / d):
+ *   seen from d = 2 with parallel rays a light of r = 0.5 shows a silhouette of radius 0.486.  Light sampling uses the same cone, so the two agree. */
 typedef struct crh_light {
   float vec[3];
   float is_point;                 /* 0 = directional, 1 = positional */
