@@ -100,12 +100,24 @@ class crh_region_stats(C.Structure):
 REGION_TOUCHED, REGION_ENCLOSED = 0, 1      # crh_region_select
 REGION_STATS_DTYPE = [("pixels", "<u4"), ("pixels_frame", "<u4"), ("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4"), ("t_min", "<f4"), ("t_max", "<f4")]   # numpy view of the records
 
+class crh_outline_params(C.Structure):
+    """the feature lines' parameters (include/cadrays_hip.h; crh_outline_defaults fills them: OUTLINE_DEFAULTS below)"""
+    _fields_ = [("kinds", C.c_uint32), ("crease_cos", C.c_float), ("depth_ratio", C.c_float), ("width", C.c_uint32), ("rgb", C.c_uint8 * 3), ("alpha", C.c_uint8)]
+
+
+OUTLINE_OBJECT, OUTLINE_DEPTH, OUTLINE_CREASE = 1, 2, 4      # crh_outline_params.kinds, the bits of crh_read_outline's mask
+OUTLINE_ALL = OUTLINE_OBJECT | OUTLINE_DEPTH | OUTLINE_CREASE
+OUTLINE_TABLE_DTYPE = [("n", "<f4", (3,)), ("degenerate", "<u4"), ("v", "<u4", (3,)), ("pad", "<u4")]      # numpy view of the per-triangle table (32 B)
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
 
 METER_DEFAULTS = dict(key_stops=_f32(-2.4739311883324122), min_stops=-10.0, max_stops=10.0, white_permille=990, white_min=1.0, white_max=10.0, rect=(0, 0, 0, 0))      # key: log2(0.18)
 
+OUTLINE_DEFAULTS = dict(kinds=OUTLINE_ALL, crease_cos=_f32(0.8660254037844387), depth_ratio=_f32(1.02), width=1, rgb=(0, 0, 0), alpha=255)      # cos 30 deg
+
+assert C.sizeof(crh_outline_params) == 20
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_region_stats) == 32
@@ -127,4 +139,5 @@ EXPORTS = [
     "crh_set_display", "crh_get_display", "crh_meter_defaults", "crh_meter_from_histogram", "crh_set_auto_exposure", "crh_measure_exposure",
     "crh_fit_view", "crh_fit_extents_host", "crh_fit_from_extents",
     "crh_query_region", "crh_region_stats_host", "crh_region_select",
+    "crh_outline_defaults", "crh_set_outline", "crh_get_outline", "crh_read_outline", "crh_outline_table_host", "crh_outline_mask_host", "crh_outline_draw_host",
 ]

@@ -75,6 +75,18 @@ def region_args(rect, poly):
     return (None if r is None else r.ctypes.data_as(_u32p), None if q is None else q.ctypes.data_as(_i32p), C.c_uint32(0 if q is None else len(q)), (r, q))
 
 
+def outline_params(**fields):
+    """abi.crh_outline_params: the defaults (abi.OUTLINE_DEFAULTS == crh_outline_defaults) with the named fields replaced; an unknown name is an error"""
+    unknown = sorted(set(fields) - set(abi.OUTLINE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"no such outline parameter {unknown}; crh_outline_params has {sorted(abi.OUTLINE_DEFAULTS)}")
+    v = dict(abi.OUTLINE_DEFAULTS); v.update(fields)
+    p = abi.crh_outline_params(int(v["kinds"]), float(v["crease_cos"]), float(v["depth_ratio"]), int(v["width"]))
+    p.rgb[:] = [int(x) for x in v["rgb"]]
+    p.alpha = int(v["alpha"])
+    return p
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -427,6 +439,29 @@ class Backend:
         out = np.zeros(int(n_objects) + 1, abi.REGION_STATS_DTYPE)
         r, q, n, _keep = region_args(rect, poly)
         self._call("query_region", r, q, n, out.ctypes.data_as(C.POINTER(abi.crh_region_stats)), C.c_uint32(int(n_objects)))
+        return out
+
+    # -- feature lines on the LDR read-out (crh_outline.cpp) -------------------------------
+    def set_outline(self, on=True, **params):
+        """crh_set_outline: every LDR read-out draws object / depth / crease lines from the id buffer (fields of crh_outline_params by name, the others take
+        crh_outline_defaults); on=False / None switches them off.  Display state: the accumulation goes on."""
+        if not on:
+            self._call("set_outline", None)
+            return
+        p = outline_params(**params)
+        self._call("set_outline", C.byref(p))
+
+    def get_outline(self):
+        """crh_get_outline: dict(kinds, crease_cos, depth_ratio, width, rgb, alpha, on) as in force (the defaults while the feature is off)"""
+        p, on = abi.crh_outline_params(), C.c_int(0)
+        self._call("get_outline", C.byref(p), C.byref(on))
+        return {"kinds": int(p.kinds), "crease_cos": np.float32(p.crease_cos), "depth_ratio": np.float32(p.depth_ratio), "width": int(p.width),
+                "rgb": tuple(int(x) for x in p.rgb), "alpha": int(p.alpha), "on": bool(on.value)}
+
+    def read_outline(self):
+        """crh_read_outline: (H, W) uint8, per pixel the OR of abi.OUTLINE_OBJECT / _DEPTH / _CREASE, all three whatever `kinds` draws"""
+        out = np.empty((self.height, self.width), np.uint8)
+        self._call("read_outline", out.ctypes.data_as(_u8p))
         return out
 
     # -- kernel-level --------------------------------------------------------------------

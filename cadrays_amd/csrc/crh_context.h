@@ -12,6 +12,8 @@
 //   crh_reduce.cpp     crh_reduce (RCCL over xGMI, or peer copies on one device)
 //   crh_pick.cpp       the first-hit id buffer: camera rays, pick, id read-back, selection / hover state and bounds, the overlay of the LDR read-out
 //   crh_fit.cpp        fit the view to the displayed / chosen objects: vertex extents on the device (fit_kernels.hip), the closed-form rule, the host-only twins
+//   crh_region.cpp     region queries on the id buffer: rectangle / lasso selection, visible objects (region_kernels.hip), the host-only twin
+//   crh_outline.cpp    feature lines on the LDR read-out: object, depth and crease edges from the id buffer (outline_kernels.hip), the host-only twins
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
@@ -242,6 +244,7 @@ struct PickState {
   DevBuf<int32_t> d_pk_tri_obj; bool pk_tri_obj_dirty = true;                                // c->tri_obj on the device (uploaded on first need after crh_build / crh_add_object)
   DevBuf<uint32_t> d_pk_cursor; DevBuf<DCounters> d_pk_counters;                             // work cursor and counter block of the id pass (crh_stats never sees its rays)
   bool ids_valid = false; uint32_t ids_w = 0, ids_h = 0;
+  uint64_t ids_gen = 0;                                                                      // bumped whenever ensure_ids recomputes: what is derived from the buffer (the outline mask) knows when it is stale
   std::vector<uint8_t> sel; bool sel_any = false; uint8_t sel_rgb[3] = {0, 0, 0}; uint32_t sel_alpha = 0;
   DevBuf<uint8_t> d_sel; bool sel_dirty = false;
   int32_t hover = -1; uint8_t hov_rgb[3] = {0, 0, 0}; uint32_t hov_alpha = 0;
@@ -259,6 +262,16 @@ struct RegionState {
   DevBuf<void> d_rg_edges; DevBuf<uint32_t> d_rg_rec;      // kRegionMaxEdges edges; kRegionRec words per record (objects + background)
 };
 
+// ---- feature lines (crh_outline.cpp): display state like the selection -- only the LDR read-out looks at it.  The per-triangle table (32 B: object-space normal and
+// vertex indices) is DERIVED from pos / tri and uploaded by the first call that needs it after the geometry changed; the mask (one byte per pixel) is derived from the
+// id buffer and the table and kept while neither, nor the frame size, nor the two thresholds change.  A host that never switches the feature on pays nothing.
+struct OutlineState {
+  bool ol_on = false; crh_outline_params ol_par{};
+  DevBuf<void> d_ol_table; uint32_t ol_n_tri = 0; bool ol_table_dirty = true; uint64_t ol_table_gen = 0;
+  DevBuf<uint8_t> d_ol_mask; bool ol_mask_valid = false;
+  uint64_t ol_mask_ids_gen = 0, ol_mask_table_gen = 0; uint32_t ol_mask_w = 0, ol_mask_h = 0; float ol_mask_crease = 0.f, ol_mask_ratio = 0.f;      // what the mask was computed from
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -269,7 +282,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -356,6 +369,8 @@ int ensure_ids(crh_ctx* c);                     // the id buffer of the state in
 int pick_stream(crh_ctx* c);                    // the side stream of the id buffer, of crh_fit_view and of crh_query_region, created on first need
 int fork_from_context(crh_ctx* c);              // ... made to start behind what the setters have put on the context's stream
 int wait_overlay_readers(crh_ctx* c);
+// ---- crh_outline.cpp
+int outline_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // feature lines over the tone-mapped bytes at d_ldr, enqueued on `on`, BEFORE overlay_ldr; nothing at all while the feature is off
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

@@ -43,7 +43,7 @@ int ensure_ids(crh_ctx* c)
   launch_first_hit_resolve(Ls, W, H, (uint32_t)n_slots, c->d_pk_hit_slot, c->tri_obj.empty() ? nullptr : c->d_pk_tri_obj, (uint32_t)c->tri_obj.size(), c->d_pk_hit, c->d_pk_obj);
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipStreamSynchronize(c->pk_stream));
-  c->ids_valid = true; c->ids_w = W; c->ids_h = H;
+  c->ids_valid = true; c->ids_w = W; c->ids_h = H; ++c->ids_gen;
   return CRH_OK;
 }
 

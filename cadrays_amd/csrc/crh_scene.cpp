@@ -270,7 +270,7 @@ int crh_set_geometry(crh_ctx* c, const float* pos, const float* nrm, const float
   if (uv) c->uv.assign(uv, uv + 2 * (size_t)nV); else c->uv.clear();
   c->tri.assign(tri, tri + 4 * (size_t)nT);
   c->two_level = false; c->nO = 0; c->xf.clear(); c->tri_obj.clear(); c->hidden.clear();      // a new scene: everything displayed
-  clear_selection(c); c->ids_valid = false; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true;      // ... nothing selected or hovered
+  clear_selection(c); c->ids_valid = false; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true; c->ol_table_dirty = true;      // ... nothing selected or hovered
   if (tri_obj && xf && nO) {
     // two-level mode: vertices stay in object space; every object gets its own tree (crh_build), the top-level tree
     // over the instances carries the transforms (crh_set_transforms rebuilds only that)
@@ -450,7 +450,7 @@ int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* 
   TwoLevelState::Obj o{}; o.first = T0; o.ntri = nT; o.static0 = false; o.in_static = false;
   c->objs.push_back(o);
   if (!c->hidden.empty()) c->hidden.push_back(0);
-  c->nO = ob + 1; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true;
+  c->nO = ob + 1; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true; c->ol_table_dirty = true;
   if (object_out) *object_out = ob;
   return apply_objects(c, nullptr, nullptr);
 }
@@ -733,6 +733,7 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
   if (c->two_level && !c->hidden.empty()) { if (c->hidden.size() != c->nO) c->hidden.assign(c->nO, 0); if ((rc = apply_objects(c, nullptr, nullptr))) return rc; }      // objects erased before the build: baked like the rest, then disabled
   rc = do_reset(c); if (rc) return rc;
   c->fit_verts_dirty = true;                             // ... and so does the vertex array of crh_fit_view (crh_fit.cpp)
+  c->ol_table_dirty = true;                              // ... and the per-triangle table of the feature lines (crh_outline.cpp)
   c->pk_tri_obj_dirty = true;                            // the triangle-to-object table of the id buffer follows the scene (crh_pick.cpp uploads it on first need)
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;

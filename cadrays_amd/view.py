@@ -146,6 +146,21 @@ class View(Backend):
         st = self.query_region(self._n_objects)
         return {int(o): {n: st[n][o].item() for n in st.dtype.names} for o in np.flatnonzero(st["pixels_frame"][:-1] >= max(int(min_pixels), 1))}
 
+    # ---- feature lines, "shaded with edges" (crh_outline.cpp; no counterpart in the reference's path tracer, DataNode.cxx:286 sets a display mode of the rasteriser) ----
+    def SetOutline(self, kinds=abi.OUTLINE_ALL, crease_deg=30.0, depth_rel=0.02, width=1, rgb=(0, 0, 0), alpha=255):
+        """lines along object boundaries, depth steps (first-hit distance larger by more than depth_rel, relative) and creases (planes meeting at more than
+        crease_deg) over every LDR read-out from now on; nothing restarts.  The angle and the step become crease_cos / depth_ratio in double, rounded once."""
+        self.set_outline(True, kinds=int(kinds), crease_cos=outline_crease_cos(crease_deg), depth_ratio=outline_depth_ratio(depth_rel), width=int(width),
+                         rgb=tuple(int(x) for x in rgb), alpha=int(alpha))
+
+    def ClearOutline(self):
+        """no lines: the LDR bytes of a view that never called SetOutline"""
+        self.set_outline(False)
+
+    def ReadOutline(self):
+        """(H, W) uint8 mask of the lines' pixels: abi.OUTLINE_OBJECT | _DEPTH | _CREASE per pixel, with the thresholds in force (the defaults while off)"""
+        return self.read_outline()
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -382,6 +397,62 @@ def region_select(stats, mode=abi.REGION_TOUCHED, min_pixels=1):
     if rc != 0:
         raise BackendError(f"crh_region_select -> {rc}")
     return flags
+
+
+def outline_crease_cos(crease_deg):
+    """the float32 crease_cos of an angle in degrees: the cosine in double, rounded once"""
+    import math
+    return float(np.float32(math.cos(math.radians(float(crease_deg)))))
+
+
+def outline_depth_ratio(depth_rel):
+    """the float32 depth_ratio of a relative step: 1 + depth_rel in double, rounded once"""
+    return float(np.float32(1.0 + float(depth_rel)))
+
+
+def outline_table_host(pos, tri):
+    """crh_outline_table_host on the host only (no GPU): pos (n, 3) float32, tri (m, 4) rows {v0, v1, v2, material} as set_geometry takes them; the per-triangle
+    table, a numpy record array of m entries (abi.OUTLINE_TABLE_DTYPE, 32 B each)"""
+    lib = load_library()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    tri = np.ascontiguousarray(np.asarray(tri).astype(np.int64) & 0xFFFFFFFF, np.uint32).reshape(-1, 4)
+    out = np.zeros(len(tri), abi.OUTLINE_TABLE_DTYPE)
+    rc = lib.crh_outline_table_host(pos.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(len(pos)), tri.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(len(tri)),
+                                    out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise BackendError(f"crh_outline_table_host -> {rc}")
+    return out
+
+
+def outline_mask_host(object_px, triangle_px, t_px, table, crease_cos=abi.OUTLINE_DEFAULTS["crease_cos"], depth_ratio=abi.OUTLINE_DEFAULTS["depth_ratio"]):
+    """crh_outline_mask_host on the host only (no GPU): the planes as read_ids returns them, each (H, W); table as outline_table_host returns it (None / empty:
+    no triangle is known); the (H, W) uint8 mask as read_outline returns it"""
+    lib = load_library()
+    ob, tr, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == tr.shape == t.shape
+    tb = np.zeros(0, abi.OUTLINE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.OUTLINE_TABLE_DTYPE)
+    out = np.zeros(ob.shape, np.uint8)
+    rc = lib.crh_outline_mask_host(ob.ctypes.data_as(C.POINTER(C.c_int32)), tr.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_float)),
+                                   C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]), tb.ctypes.data_as(C.c_void_p) if len(tb) else None, C.c_uint32(len(tb)),
+                                   C.c_float(float(crease_cos)), C.c_float(float(depth_ratio)), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise BackendError(f"crh_outline_mask_host -> {rc}")
+    return out
+
+
+def outline_draw_host(mask, ldr, **params):
+    """crh_outline_draw_host on the host only (no GPU): the lines of an (H, W) uint8 mask drawn over a copy of the (H, W, 3) uint8 image; params as in
+    Backend.set_outline (fields of crh_outline_params)"""
+    from .binding import outline_params
+    lib = load_library()
+    m = np.ascontiguousarray(mask, np.uint8)
+    img = np.array(ldr, np.uint8, order="C")
+    assert m.ndim == 2 and img.shape == m.shape + (3,)
+    p = outline_params(**params)
+    rc = lib.crh_outline_draw_host(m.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint32(m.shape[1]), C.c_uint32(m.shape[0]), C.byref(p), img.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise BackendError(f"crh_outline_draw_host -> {rc}")
+    return img
 
 
 def build_bvh_host(pos, tri, threads=0):

@@ -506,6 +506,72 @@ CRH_API int crh_region_stats_host(const int32_t* object_px, const float* t_px, u
  * The background record stats[n_objects] is not looked at.  Any other mode, a NULL or n_objects == 0: CRH_E_INVALID. */
 CRH_API int crh_region_select(const crh_region_stats* stats, uint32_t n_objects, int mode, uint32_t min_pixels, uint8_t* selected_out /* n_objects */);
 
+/* --- feature lines on the display (crh_outline.cpp, cadrays_amd/csrc/outline_kernels.hip) -----------------------------------------------------------
+ * "Shaded with edges": crisp lines along object boundaries, depth steps and creases, drawn by the LDR read-outs over the tone-mapped bytes from the first-hit id
+ * buffer of the picking section, so they stay sharp at 1 spp.  The reference has NO counterpart: OCCT's path tracer draws no edges, and DataNode.cxx:286 only sets a
+ * display mode of the rasteriser.  Display state like crh_set_display and the selection: nothing here restarts or touches the accumulation, and crh_read_hdr*,
+ * crh_save_accum and crh_reduce never see it.
+ *   TABLE: one 32-byte record per triangle in the caller's triangle order (the rows of crh_set_geometry, the rows of every crh_add_object following: the numbering
+ *   of `triangle` in the id buffer): {float n[3]; uint32_t degenerate; uint32_t v[3]; uint32_t pad}.  v = the triangle's three vertex indices as the context stores
+ *   them.  n = the unit normal in OBJECT space from the positions as handed over, in double, in this order: widen the floats; a = p1 - p0, b = p2 - p0;
+ *   c = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), each product rounded, then the difference; l = sqrt((c.x c.x + c.y c.y) + c.z c.z); if l > 0 and
+ *   finite n = (float)(c / l) per component and degenerate = 0, otherwise n = 0 and degenerate = 1.  Built and uploaded on the side stream of the id buffer by the
+ *   first call that needs it after crh_build, crh_add_object or crh_set_geometry: a host that never switches the feature on pays nothing.  A MOVED object keeps its
+ *   object-space normals: both pixels of a pair compared for a crease lie in the same object, so only a non-uniform scale changes the angle between them.
+ *   RULE, for every pair (a, b) of 4-neighbours inside the frame, a left of b or above b (nothing pairs across the frame border); hit(i) = triangle[i] >= 0, a miss
+ *   carries object -1 and t = 1e15 as the id buffer writes it:
+ *     OBJECT  object[a] != object[b] (one of them may be the background).
+ *     otherwise, if hit(a), hit(b), triangle[a] != triangle[b] and both indices lie below the table's length, two tests (a pair may set both bits):
+ *     DEPTH   no v[] of one triangle equals a v[] of the other (nine integer compares: equality of INDICES, not of positions) and hi > lo * depth_ratio, lo / hi the
+ *             smaller / larger t of the two: one float32 product, rounded, then a strict compare.
+ *     CREASE  neither record is degenerate and fabsf((n.x m.x + n.y m.y) + n.z m.z) < crease_cos in plain float32, no fused multiply-add.  The absolute value is
+ *             deliberate: meshes with inconsistent winding are common enough that the readers carry -fixnorms.
+ *     If any kind was set the MARKED pixel is b if t[b] < t[a], else a -- the line lies on the nearer surface; on a tie (coincident CAD faces included) it goes to a --
+ *     and mask[marked] |= kinds.  A pixel's byte is the OR over its up to four pairs.  No transcendental, no fma, no atomic: the device, the host twin and a numpy
+ *     restatement agree bit for bit.
+ *   KNOWN LIMIT: the depth test is a ratio of ray distances, it is not slope-aware.  An UNWELDED flat mesh (every triangle its own vertices) seen at a grazing angle,
+ *   or at a very low resolution, produces depth lines; a welded mesh does not (neighbouring triangles share an index).  A host can raise depth_ratio or drop the
+ *   DEPTH bit.
+ *   DRAWING: the window of a pixel has offsets dx, dy in [-floor((width - 1) / 2), ceil((width - 1) / 2)], cut to the frame: the pixel itself for width 1, 2 x 2 for
+ *   width 2, 3 x 3 centred for width 3.  A pixel is drawn iff some pixel of its window has mask & kinds != 0; a drawn pixel becomes, per channel, the colour if
+ *   alpha == 255, otherwise (ldr * (256 - alpha) + colour * alpha + 128) >> 8, the selection interior's formula.  Read-out order: metering, tone map,
+ *   ShowSamplingTiles outline, feature lines, selection, hover.  Multi-GPU: as for the selection, the context that serves the LDR read-out draws. */
+#define CRH_OUTLINE_OBJECT 1u   /* the two pixels belong to different objects (or one is background) */
+#define CRH_OUTLINE_DEPTH  2u   /* same object, unconnected triangles, a step in first-hit distance  */
+#define CRH_OUTLINE_CREASE 4u   /* same object, the two triangles' planes meet at a sharp angle      */
+typedef struct crh_outline_params {
+  uint32_t kinds;        /* which of the three are DRAWN; 0 draws nothing                       */
+  float    crease_cos;   /* in (0, 1]: crease iff |n_a . n_b| < crease_cos; default cos 30 deg  */
+  float    depth_ratio;  /* >= 1, finite: step iff max(t) > min(t) * depth_ratio; default 1.02  */
+  uint32_t width;        /* 1, 2 or 3 pixels                                                    */
+  uint8_t  rgb[3], alpha;/* alpha 255 = the colour itself; default black, 255                   */
+} crh_outline_params;    /* 20 B */
+/* (no counterpart in the reference: DataNode.cxx:286 sets a display mode of the rasteriser)  all three kinds, cos 30 deg, 1.02, width 1, black, alpha 255 */
+CRH_API void crh_outline_defaults(crh_outline_params* p);
+/* (no counterpart in the reference: DataNode.cxx:286)  Switch the lines on with these parameters, or off with NULL -- the state of a new context.  Display state:
+ * no restart, no work on any stream, allowed before crh_build; with the feature off, with kinds == 0 or before crh_build the LDR bytes are exactly those of a
+ * context that never called it.  CRH_E_INVALID with a message: unknown bits in kinds, width outside 1..3, crease_cos outside (0, 1], depth_ratio below 1, a NaN
+ * or Inf anywhere.  The mask is computed by the first LDR read-out that needs it and kept while the id buffer, the table, the frame size, crease_cos and
+ * depth_ratio stay what they were: changing only kinds, width or the colour recomputes nothing. */
+CRH_API int crh_set_outline(crh_ctx* ctx, const crh_outline_params* p /* NULL = off */);
+/* (no counterpart in the reference)  The parameters in force (the defaults while the feature is off) and whether it is on; either pointer may be NULL. */
+CRH_API int crh_get_outline(crh_ctx* ctx, crh_outline_params* out, int* on);
+/* (no counterpart in the reference)  The mask itself, W*H bytes, row 0 = top: per pixel the OR of the three bits, ALL three whatever `kinds` says (kinds only filters
+ * the drawing), with the thresholds in force, or the defaults while the feature is off.  Needs a built scene (CRH_E_NOTBUILT).  Runs on the side stream of the id
+ * buffer; synchronous; a stale id buffer is computed first exactly as crh_pick would.  Accumulator, frame counter, samples traced ahead, crh_stats, the selection and
+ * read-backs in flight are not touched. */
+CRH_API int crh_read_outline(crh_ctx* ctx, uint8_t* mask_out /* W*H */);
+/* Host-only, no device and no context (no counterpart in the reference): the table of the rule above.  pos: 3 floats per vertex; tri: 4 words per triangle as
+ * crh_set_geometry takes them {v0, v1, v2, material}, the material is not read; an index >= n_vertices, a NULL or n_tri == 0: CRH_E_INVALID. */
+CRH_API int crh_outline_table_host(const float* pos, uint32_t n_vertices, const uint32_t* tri, uint32_t n_tri, void* table_out /* 32 B per triangle */);
+/* Host-only (no counterpart in the reference): the mask of the rule above over caller-supplied planes as crh_read_ids returns them -- the same function the kernel
+ * compiles, in a plain loop, one thread.  table may be NULL with n_tri == 0 (then only OBJECT is ever set); a triangle index outside [0, n_tri) takes part in no
+ * same-object test.  width, height >= 1; crease_cos in (0, 1], depth_ratio >= 1, both finite; anything else CRH_E_INVALID. */
+CRH_API int crh_outline_mask_host(const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height,
+                          const void* table, uint32_t n_tri, float crease_cos, float depth_ratio, uint8_t* mask_out /* width*height */);
+/* Host-only (no counterpart in the reference): the drawing rule above over a mask, in place on RGB8 bytes.  p is checked as crh_set_outline checks it. */
+CRH_API int crh_outline_draw_host(const uint8_t* mask, uint32_t width, uint32_t height, const crh_outline_params* p, uint8_t* ldr_inout /* width*height*3 */);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
