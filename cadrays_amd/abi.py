@@ -109,6 +109,11 @@ OUTLINE_OBJECT, OUTLINE_DEPTH, OUTLINE_CREASE = 1, 2, 4      # crh_outline_param
 OUTLINE_ALL = OUTLINE_OBJECT | OUTLINE_DEPTH | OUTLINE_CREASE
 OUTLINE_TABLE_DTYPE = [("n", "<f4", (3,)), ("degenerate", "<u4"), ("v", "<u4", (3,)), ("pad", "<u4")]      # numpy view of the per-triangle table (32 B)
 
+class crh_denoise_params(C.Structure):
+    """the denoised display's parameters (include/cadrays_hip.h; crh_denoise_defaults fills them: DENOISE_DEFAULTS below)"""
+    _fields_ = [("levels", C.c_uint32), ("normal_cos", C.c_float), ("depth_ratio", C.c_float), ("until_samples", C.c_uint32)]
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -117,7 +122,9 @@ METER_DEFAULTS = dict(key_stops=_f32(-2.4739311883324122), min_stops=-10.0, max_
 
 OUTLINE_DEFAULTS = dict(kinds=OUTLINE_ALL, crease_cos=_f32(0.8660254037844387), depth_ratio=_f32(1.02), width=1, rgb=(0, 0, 0), alpha=255)      # cos 30 deg
 
-assert C.sizeof(crh_outline_params) == 20
+DENOISE_DEFAULTS = dict(levels=4, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05), until_samples=256)      # cos 25 deg
+
+assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_region_stats) == 32
@@ -140,4 +147,5 @@ EXPORTS = [
     "crh_fit_view", "crh_fit_extents_host", "crh_fit_from_extents",
     "crh_query_region", "crh_region_stats_host", "crh_region_select",
     "crh_outline_defaults", "crh_set_outline", "crh_get_outline", "crh_read_outline", "crh_outline_table_host", "crh_outline_mask_host", "crh_outline_draw_host",
+    "crh_denoise_defaults", "crh_set_denoise", "crh_get_denoise", "crh_read_denoised", "crh_denoise_host", "crh_bench_denoise",
 ]

@@ -87,6 +87,15 @@ def outline_params(**fields):
     return p
 
 
+def denoise_params(**fields):
+    """abi.crh_denoise_params: the defaults (abi.DENOISE_DEFAULTS == crh_denoise_defaults) with the named fields replaced; an unknown name is an error"""
+    unknown = sorted(set(fields) - set(abi.DENOISE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"no such denoise parameter {unknown}; crh_denoise_params has {sorted(abi.DENOISE_DEFAULTS)}")
+    v = dict(abi.DENOISE_DEFAULTS); v.update(fields)
+    return abi.crh_denoise_params(int(v["levels"]), float(v["normal_cos"]), float(v["depth_ratio"]), int(v["until_samples"]))
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -463,6 +472,35 @@ class Backend:
         out = np.empty((self.height, self.width), np.uint8)
         self._call("read_outline", out.ctypes.data_as(_u8p))
         return out
+
+    # -- denoised display in front of the LDR read-outs' tone map (crh_denoise.cpp) -----------
+    def set_denoise(self, on=True, **params):
+        """crh_set_denoise: every LDR read-out tone-maps the id-guided a-trous filter of the accumulator (fields of crh_denoise_params by name, the others take
+        crh_denoise_defaults); on=False / None switches it off.  Display state: the accumulation goes on, and nothing but the LDR bytes changes."""
+        if not on:
+            self._call("set_denoise", None)
+            return
+        p = denoise_params(**params)
+        self._call("set_denoise", C.byref(p))
+
+    def get_denoise(self):
+        """crh_get_denoise: dict(levels, normal_cos, depth_ratio, until_samples, on) as in force (the defaults while the feature is off)"""
+        p, on = abi.crh_denoise_params(), C.c_int(0)
+        self._call("get_denoise", C.byref(p), C.byref(on))
+        return {"levels": int(p.levels), "normal_cos": np.float32(p.normal_cos), "depth_ratio": np.float32(p.depth_ratio), "until_samples": int(p.until_samples),
+                "on": bool(on.value)}
+
+    def read_denoised(self):
+        """crh_read_denoised: (H, W, 4) float32 (r, g, b, w), the image the tone map of a read_ldr issued now would read (the defaults while the feature is off)"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._call("read_denoised", _fp(out))
+        return out
+
+    def bench_denoise(self, repeats=20):
+        """crh_bench_denoise: dict(guide_ms, pass_ms) -- device time per launch of the guide kernel and of every pass of the parameters in force (HIP events)"""
+        g, p = C.c_float(0), (C.c_float * 5)()
+        self._call("bench_denoise", C.c_uint32(int(repeats)), C.byref(g), p)
+        return {"guide_ms": float(g.value), "pass_ms": [float(x) for x in p]}
 
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):

@@ -14,6 +14,7 @@
 //   crh_fit.cpp        fit the view to the displayed / chosen objects: vertex extents on the device (fit_kernels.hip), the closed-form rule, the host-only twins
 //   crh_region.cpp     region queries on the id buffer: rectangle / lasso selection, visible objects (region_kernels.hip), the host-only twin
 //   crh_outline.cpp    feature lines on the LDR read-out: object, depth and crease edges from the id buffer (outline_kernels.hip), the host-only twins
+//   crh_denoise.cpp    the denoised display: an id-guided a-trous filter in front of the LDR read-outs' tone map (denoise_kernels.hip), the host-only twin
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
@@ -272,6 +273,18 @@ struct OutlineState {
   uint64_t ol_mask_ids_gen = 0, ol_mask_table_gen = 0; uint32_t ol_mask_w = 0, ol_mask_h = 0; float ol_mask_crease = 0.f, ol_mask_ratio = 0.f;      // what the mask was computed from
 };
 
+// ---- denoised display (crh_denoise.cpp): display state like the feature lines -- only the tone map of an LDR read-out (and crh_read_denoised) looks at it.  The guide
+// (per pixel {n.xyz, t} and {object, triangle}) is DERIVED from the id buffer and the per-triangle table of the feature lines and kept while neither, nor the frame
+// size, changes.  Two ping-pong images per SET: set 0 serves the synchronous read-outs on the context's stream, set 1 the read-back stream, whose two slots are serial
+// in stream order and so share it.  A host that never switches the feature on pays nothing.
+struct DenoiseState {
+  bool dn_on = false; crh_denoise_params dn_par{};
+  DevBuf<float4> d_dn_guide; DevBuf<int2> d_dn_ids; bool dn_guide_valid = false;
+  uint64_t dn_guide_ids_gen = 0, dn_guide_table_gen = 0; uint32_t dn_guide_w = 0, dn_guide_h = 0;      // what the guide was computed from
+  DevBuf<float4> d_dn_img[2][2];
+  bool dn_staged = true;            // steps 1 and 2 take the LDS-staged kernel (denoise_kernels.hip): 67 - 72 against 77 - 85 us per pass at 1080p; CRH_DENOISE_STAGED=0: the plain gather; the same bytes either way
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -282,7 +295,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -371,6 +384,12 @@ int fork_from_context(crh_ctx* c);              // ... made to start behind what
 int wait_overlay_readers(crh_ctx* c);
 // ---- crh_outline.cpp
 int outline_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // feature lines over the tone-mapped bytes at d_ldr, enqueued on `on`, BEFORE overlay_ldr; nothing at all while the feature is off
+int ensure_outline_table(crh_ctx* c);                              // the per-triangle table of the geometry in force, built and uploaded on first need (after ensure_ids)
+// ---- crh_denoise.cpp
+// The image the tone map of an LDR read-out reads, in *shown: `src` itself while the feature is off or there is no scene (nothing is allocated, nothing is launched),
+// else the filtered image of scratch set `set` (0: the context's stream, 1: the read-back stream), its passes enqueued on `on`.  Called just BEFORE launch_tonemap,
+// after the metering, which keeps reading `src`.
+int denoise_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown);
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

@@ -1,0 +1,196 @@
+// crh_denoise.cpp -- the denoised display: an a-trous filter in front of the tone map of the LDR read-outs, guided by the first-hit id buffer and the per-triangle
+// normals of the feature lines' table, so that the 1 - 4 spp frames of a camera drag lose their salt and pepper while object boundaries, creases and depth steps stay
+// crisp.  The reference has no counterpart: OCCT's path tracer shows the raw accumulation (AppViewer.cxx:979-984 restarts it on every camera move, :1045-1047 shows it).
+// Two kernels (denoise_kernels.hip): the guide -- per pixel what a tap needs, derived from the id buffer and the table, kept until one of them changes -- and one
+// pass per level.  The rules have ONE copy (denoise_kernels.h), compiled for the kernels and for the host twin below.  Display state: nothing of the rendering
+// state is touched, and only the tone map's source changes.  DESIGN.md section 4.12.
+// (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
+#include <new>
+
+#include "crh_context.h"
+#include "denoise_kernels.h"
+
+using namespace crh;
+using namespace crh::api;
+
+static_assert(sizeof(crh_denoise_params) == 16, "crh_denoise_params is 16 bytes");
+static_assert(sizeof(float4) == 16 && sizeof(int2) == 8, "the guide record is 16 + 8 bytes");
+
+namespace {
+
+const char* params_refused(const crh_denoise_params* p)
+{
+  const float f[] = {p->normal_cos, p->depth_ratio};
+  if (!all_finite(f, 2)) return "normal_cos / depth_ratio hold a NaN / Inf";
+  if (p->levels < 1u || p->levels > kDenoiseMaxLevels) return "levels lies outside 1..5";
+  if (!(p->normal_cos > 0.f && p->normal_cos <= 1.f)) return "normal_cos lies outside (0, 1]";
+  if (!(p->depth_ratio >= 1.f)) return "depth_ratio is below 1";
+  if (p->until_samples < 1u || p->until_samples > (1u << 20)) return "until_samples lies outside 1..2^20";
+  return nullptr;
+}
+
+DenoiseRule rule_of(const crh_denoise_params& p) { return DenoiseRule{p.levels, p.normal_cos, p.depth_ratio, (float)p.until_samples}; }      // (2^20 is exact)
+
+// The guide of the state in force, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids and the outline mask are).
+int ensure_guide(crh_ctx* c)
+{
+  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
+  CRH_HIP(hipSetDevice(c->device));
+  if ((rc = pick_stream(c))) return rc;
+  if ((rc = ensure_outline_table(c))) return rc;
+  const uint32_t W = c->par.width, H = c->par.height;
+  if (c->dn_guide_valid && c->dn_guide_ids_gen == c->ids_gen && c->dn_guide_table_gen == c->ol_table_gen && c->dn_guide_w == W && c->dn_guide_h == H) return CRH_OK;
+  if ((rc = wait_overlay_readers(c))) return rc;         // an asynchronous read-back may still be filtering from the guide
+  c->dn_guide_valid = false;
+  CRH_HIP(c->d_dn_guide.reserve((size_t)W * H)); CRH_HIP(c->d_dn_ids.reserve((size_t)W * H));      // (what read the old blocks has been waited for: the synchronous
+  launch_denoise_guide(c->pk_stream, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids);      //  read-outs end with a wait, the readers just above)
+  CRH_HIP(hipGetLastError());
+  CRH_HIP(hipStreamSynchronize(c->pk_stream));
+  c->dn_guide_valid = true; c->dn_guide_ids_gen = c->ids_gen; c->dn_guide_table_gen = c->ol_table_gen; c->dn_guide_w = W; c->dn_guide_h = H;
+  return CRH_OK;
+}
+
+// The passes of rule R from `src` through the two images of scratch set `set`, enqueued on `on`; *shown = the image the last pass wrote.
+int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const DenoiseRule& R, const float4** shown)
+{
+  if (int rc = ensure_guide(c)) return rc;
+  const uint32_t W = c->par.width, H = c->par.height;
+  const size_t n = (size_t)W * H;
+  DevBuf<float4>* img = c->d_dn_img[set];
+  if (img[0].cap() < n || img[1].cap() < n) {
+    // Set 0 is read and written on the context's stream by calls that end with a wait for it: nothing is in flight.  Set 1 belongs to the read-back stream.
+    if (set == 1) CRH_HIP(hipStreamSynchronize(c->rb_stream));
+    CRH_HIP(img[0].reserve(n)); CRH_HIP(img[1].reserve(n));
+  }
+  const float4* in = src;
+  for (uint32_t k = 0; k < R.levels; ++k) {
+    float4* out = img[k & 1u];
+    launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged);
+    in = out;
+  }
+  CRH_HIP(hipGetLastError());
+  *shown = in;
+  return CRH_OK;
+}
+
+}  // namespace
+
+namespace crh {
+namespace api {
+
+// Called by the LDR read-outs between the metering and the tone map, on the stream the tone map runs on.  Feature off or no scene: nothing is allocated, nothing is
+// launched -- the tone map reads `src`.
+// THE ACCUMULATE GUARD: the asynchronous read-out records its rb_tm event -- the one the next accumulate waits for -- after the tone map and the overlays, so it
+// already covers the first pass's read of the accumulator; no event of the filter's own is needed.
+int denoise_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown)
+{
+  *shown = src;
+  if (!c->dn_on || !c->built) return CRH_OK;
+  return filter(c, on, src, set, rule_of(c->dn_par), shown);
+}
+
+}  // namespace api
+}  // namespace crh
+
+extern "C" {
+
+void crh_denoise_defaults(crh_denoise_params* p)
+{
+  if (!p) return;
+  p->levels = 4u;
+  p->normal_cos = 0.90630778704f;      // cos 25 deg
+  p->depth_ratio = 1.05f;
+  p->until_samples = 256u;
+}
+
+int crh_set_denoise(crh_ctx* c, const crh_denoise_params* p)
+{
+  if (!c) return CRH_E_INVALID;
+  if (!p) { c->dn_on = false; return CRH_OK; }
+  if (const char* why = params_refused(p)) { std::string m = std::string("crh_set_denoise: ") + why; return fail(c, CRH_E_INVALID, m.c_str()); }
+  c->dn_par = *p; c->dn_on = true;      // read by the LDR read-outs and crh_read_denoised only
+  return CRH_OK;
+}
+
+int crh_get_denoise(crh_ctx* c, crh_denoise_params* out, int* on)
+{
+  if (!c) return CRH_E_INVALID;
+  if (out) { if (c->dn_on) *out = c->dn_par; else crh_denoise_defaults(out); }
+  if (on) *on = c->dn_on ? 1 : 0;
+  return CRH_OK;
+}
+
+int crh_read_denoised(crh_ctx* c, float* rgba_out)
+{
+  if (!c || !rgba_out) return fail(c, CRH_E_INVALID, "crh_read_denoised: null output");
+  if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
+  if (!c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
+  c->read_since_render = true;
+  crh_denoise_params p; crh_denoise_defaults(&p);
+  if (c->dn_on) p = c->dn_par;
+  CRH_HIP(hipSetDevice(c->device));
+  const float4* shown = nullptr;
+  hipStream_t on = cstream(c);
+  if (int rc = filter(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, rule_of(p), &shown)) return rc;
+  CRH_HIP(hipMemcpyAsync(rgba_out, shown, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, on));
+  CRH_HIP(hipStreamSynchronize(on));
+  return CRH_OK;
+}
+
+int crh_bench_denoise(crh_ctx* c, uint32_t repeats, float* guide_ms, float* pass_ms)
+{
+  if (!c || !repeats || !pass_ms) return fail(c, CRH_E_INVALID, "crh_bench_denoise: null output / no repeats");
+  if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
+  if (!c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
+  crh_denoise_params p; crh_denoise_defaults(&p);
+  if (c->dn_on) p = c->dn_par;
+  const DenoiseRule R = rule_of(p);
+  CRH_HIP(hipSetDevice(c->device));
+  hipStream_t on = cstream(c);
+  const float4* shown = nullptr;
+  if (int rc = filter(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, R, &shown)) return rc;      // guide and images exist, the code is loaded
+  if (int rc = wait_overlay_readers(c)) return rc;                                                            // the guide is rewritten below, with what it holds
+  CRH_HIP(hipStreamSynchronize(on));
+  const uint32_t W = c->par.width, H = c->par.height;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  CRH_HIP(hipEventCreate(&e0));
+  hipError_t e = hipEventCreate(&e1);
+  float ms = 0.f;
+  auto timed = [&](auto&& launch, float* out) {
+    if (e == hipSuccess) e = hipEventRecord(e0, on);
+    for (uint32_t r = 0; r < repeats && e == hipSuccess; ++r) { launch(); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipEventRecord(e1, on);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (out) *out = ms / (float)repeats;
+  };
+  timed([&] { launch_denoise_guide(on, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids); }, guide_ms);
+  const float4* in = c->assembled_valid ? c->d_assembled : c->d_accum;
+  for (uint32_t k = 0; k < kDenoiseMaxLevels; ++k) pass_ms[k] = 0.f;
+  for (uint32_t k = 0; k < R.levels; ++k) {          // pass k from the image pass k - 1 left, over and over: the same bytes every time
+    float4* out = c->d_dn_img[0][k & 1u];
+    timed([&] { launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged); }, &pass_ms[k]);
+    in = out;
+  }
+  const hipError_t e2 = hipStreamSynchronize(on);     // whatever went wrong: nothing still uses the two events when they go
+  hipEventDestroy(e0); if (e1) hipEventDestroy(e1);
+  CRH_HIP(e); CRH_HIP(e2);
+  return CRH_OK;
+}
+
+int crh_denoise_host(const float* rgba, const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height, const void* table,
+                     uint32_t n_tri, const crh_denoise_params* p, float* rgba_out)
+{
+  if (!rgba || !object_px || !triangle_px || !t_px || !rgba_out || !p || !width || !height || (n_tri && !table)) return CRH_E_INVALID;
+  if (params_refused(p)) return CRH_E_INVALID;
+  const size_t n = (size_t)width * height;
+  std::vector<OutlineTri> tb; std::vector<float4> in, tmp, out;      // (the caller's bytes need not be aligned)
+  try { tb.resize(n_tri); in.resize(n); tmp.resize(n); out.resize(n); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
+  if (n_tri) std::memcpy(tb.data(), table, sizeof(OutlineTri) * (size_t)n_tri);
+  std::memcpy(in.data(), rgba, sizeof(float4) * n);
+  denoise_host(object_px, triangle_px, t_px, width, height, tb.data(), n_tri, rule_of(*p), in.data(), tmp.data(), out.data());
+  std::memcpy(rgba_out, out.data(), sizeof(float4) * n);
+  return CRH_OK;
+}
+
+}  // extern "C"

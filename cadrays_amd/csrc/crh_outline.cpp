@@ -47,13 +47,16 @@ bool build_table(const float* pos, size_t n_vertices, const uint32_t* tri, size_
   return true;
 }
 
-// The mask of the state in force for these thresholds, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids does).
-int ensure_mask(crh_ctx* c, float crease_cos, float depth_ratio)
+}  // namespace
+
+namespace crh {
+namespace api {
+
+// The per-triangle table of the geometry in force, on the device, valid when this returns (the side stream exists: ensure_ids comes first).  Shared with the
+// denoised display (crh_denoise.cpp), which reads the normals.
+int ensure_outline_table(crh_ctx* c)
 {
-  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
-  CRH_HIP(hipSetDevice(c->device));
-  if ((rc = pick_stream(c))) return rc;
-  const uint32_t W = c->par.width, H = c->par.height;
+  int rc;
   if (c->ol_table_dirty) {                               // the first need after the geometry changed: build the table and upload it
     const size_t nT = c->tri.size() / 4;
     std::vector<OutlineTri> table;
@@ -66,6 +69,22 @@ int ensure_mask(crh_ctx* c, float crease_cos, float depth_ratio)
     CRH_HIP(hipStreamSynchronize(c->pk_stream));         // `table` is a temporary
     c->ol_n_tri = (uint32_t)nT; c->ol_table_dirty = false; ++c->ol_table_gen;
   }
+  return CRH_OK;
+}
+
+}  // namespace api
+}  // namespace crh
+
+namespace {
+
+// The mask of the state in force for these thresholds, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids does).
+int ensure_mask(crh_ctx* c, float crease_cos, float depth_ratio)
+{
+  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
+  CRH_HIP(hipSetDevice(c->device));
+  if ((rc = pick_stream(c))) return rc;
+  const uint32_t W = c->par.width, H = c->par.height;
+  if ((rc = ensure_outline_table(c))) return rc;
   if (c->ol_mask_valid && c->ol_mask_ids_gen == c->ids_gen && c->ol_mask_table_gen == c->ol_table_gen && c->ol_mask_w == W && c->ol_mask_h == H &&
       crh_f2u(c->ol_mask_crease) == crh_f2u(crease_cos) && crh_f2u(c->ol_mask_ratio) == crh_f2u(depth_ratio))
     return CRH_OK;

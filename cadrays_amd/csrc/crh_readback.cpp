@@ -67,7 +67,10 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   const uint8_t* d_mask = overlay ? c->d_picked : nullptr;            // written by the device-side tile draw of the last iteration
   Launch L{cstream(c), c->grid, false};
   const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
-  launch_tonemap(L, src, c->d_scratch.as<uint8_t>(), n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, meter_in_front(c, L, src, 0));
+  const float* metered = meter_in_front(c, L, src, 0);               // auto exposure meters the UNFILTERED image ...
+  const float4* shown;
+  if (int rc = denoise_src(c, L.stream, src, 0, &shown)) return rc;   // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
+  launch_tonemap(L, shown, c->d_scratch.as<uint8_t>(), n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, metered);
   if (int rc = outline_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // feature lines (crh_outline.cpp): nothing at all while the feature is off
   if (int rc = overlay_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
   CRH_HIP(hipMemcpyAsync(out, c->d_scratch, 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
@@ -108,7 +111,10 @@ static int read_begin(crh_ctx* c, bool hdr)
   else {
     const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
     const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
-    launch_tonemap(L, src, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, meter_in_front(c, L, src, 1 + (int)slot));
+    const float* metered = meter_in_front(c, L, src, 1 + (int)slot);
+    const float4* shown;
+    if (int rc = denoise_src(c, c->rb_stream, src, 1, &shown)) return rc;      // the denoised display (crh_denoise.cpp); rb_tm below covers its read of the accumulator
+    launch_tonemap(L, shown, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, metered);
     if (int rc = outline_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // feature lines (crh_outline.cpp)
     if (int rc = overlay_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // hover / selection (crh_pick.cpp)
   }

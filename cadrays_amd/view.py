@@ -161,6 +161,21 @@ class View(Backend):
         """(H, W) uint8 mask of the lines' pixels: abi.OUTLINE_OBJECT | _DEPTH | _CREASE per pixel, with the thresholds in force (the defaults while off)"""
         return self.read_outline()
 
+    # ---- denoised display (crh_denoise.cpp; no counterpart in the reference: OCCT's path tracer shows the raw accumulation) ----
+    def SetDenoise(self, levels=4, normal_deg=25.0, depth_rel=0.05, until_samples=256):
+        """an id-guided a-trous filter in front of the tone map of every LDR read-out from now on: taps mix within an object, across triangles whose planes meet at
+        less than normal_deg and whose first-hit distances differ by at most depth_rel (relative); level k works on a pixel while samples * 4^k < until_samples.
+        Nothing restarts.  The angle and the step become normal_cos / depth_ratio in double, rounded once."""
+        self.set_denoise(True, levels=int(levels), normal_cos=outline_crease_cos(normal_deg), depth_ratio=outline_depth_ratio(depth_rel), until_samples=int(until_samples))
+
+    def ClearDenoise(self):
+        """the raw accumulation: the LDR bytes of a view that never called SetDenoise"""
+        self.set_denoise(False)
+
+    def ReadDenoised(self):
+        """(H, W, 4) float32: the image the tone map of an LDR read-out issued now would read, with the parameters in force (the defaults while off)"""
+        return self.read_denoised()
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -453,6 +468,26 @@ def outline_draw_host(mask, ldr, **params):
     if rc != 0:
         raise BackendError(f"crh_outline_draw_host -> {rc}")
     return img
+
+
+def denoise_host(rgba, object_px, triangle_px, t_px, table, **params):
+    """crh_denoise_host on the host only (no GPU): rgba (H, W, 4) float32 as save_accum returns it, the planes as read_ids returns them, table as
+    outline_table_host returns it (None / empty: no triangle has a normal); params as in Backend.set_denoise (fields of crh_denoise_params); the (H, W, 4)
+    float32 image read_denoised returns"""
+    from .binding import denoise_params
+    lib = load_library()
+    img = np.ascontiguousarray(rgba, np.float32)
+    ob, tr, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == tr.shape == t.shape and img.shape == ob.shape + (4,)
+    tb = np.zeros(0, abi.OUTLINE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.OUTLINE_TABLE_DTYPE)
+    p = denoise_params(**params)
+    out = np.zeros(img.shape, np.float32)
+    rc = lib.crh_denoise_host(img.ctypes.data_as(C.POINTER(C.c_float)), ob.ctypes.data_as(C.POINTER(C.c_int32)), tr.ctypes.data_as(C.POINTER(C.c_int32)),
+                              t.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]), tb.ctypes.data_as(C.c_void_p) if len(tb) else None,
+                              C.c_uint32(len(tb)), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise BackendError(f"crh_denoise_host -> {rc}")
+    return out
 
 
 def build_bvh_host(pos, tri, threads=0):

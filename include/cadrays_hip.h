@@ -572,6 +572,69 @@ CRH_API int crh_outline_mask_host(const int32_t* object_px, const int32_t* trian
 /* Host-only (no counterpart in the reference): the drawing rule above over a mask, in place on RGB8 bytes.  p is checked as crh_set_outline checks it. */
 CRH_API int crh_outline_draw_host(const uint8_t* mask, uint32_t width, uint32_t height, const crh_outline_params* p, uint8_t* ldr_inout /* width*height*3 */);
 
+/* --- denoised display (crh_denoise.cpp, cadrays_amd/csrc/denoise_kernels.hip) ----------------------------------------------------------------------
+ * An a-trous filter in front of the LDR read-outs' tone map, guided by the first-hit id buffer of the picking section and the per-triangle normals of the feature
+ * lines' table: the 1 - 4 spp images of a camera drag lose their salt and pepper, and no colour ever crosses an object boundary, a crease or a depth step.  The
+ * reference has NO counterpart: OCCT's path tracer shows the raw accumulation.  Display state like crh_set_display, the selection and the feature lines: ONLY the
+ * image the tone map reads changes.  The metering of auto exposure keeps reading the UNFILTERED accumulator ("crh_measure_exposure + crh_set_display gives the bytes
+ * auto exposure would have produced" stays true with the filter on); crh_read_hdr*, crh_save_accum, crh_reduce, crh_accum_device_ptr, the tile statistics, the id
+ * buffer, crh_stats and the frame counter never see the filter.  Read-out order: metering (unfiltered), FILTER, tone map, ShowSamplingTiles outline, feature
+ * lines, selection, hover.  With the feature off, never set, or before crh_build nothing is allocated and nothing is launched: the LDR bytes are those of a context
+ * that never heard of it.
+ *   INPUTS per pixel i: the accumulator a[i] = (r, g, b, w), w the sample count (the assembled frame of crh_reduce takes its place while it is valid); object[i],
+ *   triangle[i], t[i] of the id buffer; the table record of triangle[i] (layout: the feature lines' TABLE above); has_n(i) = 0 <= triangle[i] < n_tri and the record
+ *   is not degenerate.
+ *   similar(p, q), symmetric, true iff all of: object[p] == object[q]; triangle[p] >= 0 and triangle[q] >= 0; and either triangle[p] == triangle[q], or all three of
+ *   has_n(p) and has_n(q); fabsf((n.x m.x + n.y m.y) + n.z m.z) >= normal_cos in plain float32, the feature lines' order and their absolute value (meshes with
+ *   inconsistent winding); not hi > lo * depth_ratio, lo / hi the smaller / larger t: one rounded float32 product, then a strict compare.
+ *   PASS k = 0 .. levels - 1, step s = 1 << k, from image `in` (the accumulator for k = 0) to image `out`, taps h = {1, 4, 6, 4, 1}:
+ *     PASS-THROUGH  out[p] = in[p], all four floats bitwise, when any of: triangle[p] < 0 (background and environment map stay sharp); !(w[p] > 0); any of
+ *                   in[p].rgb is NaN or +-Inf; !(w[p] * (float)(1u << 2k) < (float)until_samples).  The last one drops the coarse levels first as samples arrive:
+ *                   with the defaults level 3 works below 4 spp, level 2 below 16, level 1 below 64, level 0 below 256, and from 256 spp on the displayed image IS
+ *                   the accumulator, bit for bit.
+ *     FILTER        otherwise sr = sg = sb = 0.0f, uint32 Wsum = 0; dy = -2 .. 2 outer, dx = -2 .. 2 inner, q = (x + dx s, y + dy s); q is skipped if it lies outside
+ *                   the frame (nothing wraps), !(a[q].w > 0), any of in[q].rgb is not finite, or !similar(p, q); otherwise c = h[dy + 2] * h[dx + 2], an integer
+ *                   in {1, 4, 6, 16, 24, 36} exact as a float, sr = sr + c * in[q].r -- the product rounded, then the sum rounded -- likewise g and b, Wsum += c.
+ *     OUTPUT        out[p] = (sr / (float)Wsum, sg / (float)Wsum, sb / (float)Wsum, in[p].w).  The centre always counts: Wsum >= 36.  The division is the plain a / b.
+ *   BINARY edge-stopping weights, INTEGER spline weights; no exp, no fused multiply-add, no atomic, no variance estimate, no temporal reprojection.  Every pixel GATHERS:
+ *   nothing is scattered and nothing depends on the order of arrival, so the device, the host twin and a numpy restatement agree bit for bit.
+ *   KNOWN LIMITS: diffuse textures are smoothed until the thresholds pass (there is no albedo demodulation); a surface at a grazing angle filters less along the view
+ *   direction (the depth test is a ratio of ray distances, as in the feature lines); an unwelded faceted mesh filters per facet only when normal_cos excludes its
+ *   neighbours; at each level's sample threshold the displayed image changes by a small step; a POSITIONAL LIGHT IN VIEW is not in the id buffer -- a light a camera
+ *   ray passes replaces the hit in the image only (crh_light) -- so its disc is filtered as part of the surface behind it: dimmed, and smeared over that surface. */
+typedef struct crh_denoise_params {
+  uint32_t levels;         /* 1..5 passes (steps 1, 2, 4, 8, 16); default 4                                       */
+  float    normal_cos;     /* in (0, 1]: two triangles' taps mix iff |n_a . n_b| >= normal_cos; default cos 25 deg */
+  float    depth_ratio;    /* >= 1, finite: ... and not max(t) > min(t) * depth_ratio; default 1.05                */
+  uint32_t until_samples;  /* 1..2^20: level k filters a pixel while w * 4^k < until_samples; default 256          */
+} crh_denoise_params;      /* 16 B */
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  4 levels, cos 25 deg, 1.05, 256 */
+CRH_API void crh_denoise_defaults(crh_denoise_params* p);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  Switch the filter on with these parameters, or off with NULL -- the state of
+ * a new context.  Display state: no restart, no work on any stream, allowed before crh_build.  CRH_E_INVALID with a message: levels outside 1..5, normal_cos outside
+ * (0, 1], depth_ratio below 1, until_samples outside 1..2^20, a NaN or Inf anywhere.  The guide (per pixel normal, distance, object, triangle) is computed by the
+ * first read-out that needs it and kept while the id buffer, the table and the frame size stay what they were: changing the parameters recomputes nothing. */
+CRH_API int crh_set_denoise(crh_ctx* ctx, const crh_denoise_params* p /* NULL = off */);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The parameters in force (the defaults while the feature is off) and whether it
+ * is on; either pointer may be NULL. */
+CRH_API int crh_get_denoise(crh_ctx* ctx, crh_denoise_params* out, int* on);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The image the tone map of a crh_read_ldr issued now would read, W*H*4 floats
+ * (r, g, b, w), row 0 = top, with the parameters in force, or the defaults while the feature is off.  Synchronous; runs on the context's stream, ordered after
+ * everything submitted, like crh_read_ldr; a stale id buffer or table is computed first, as crh_read_outline does.  Needs a built scene (CRH_E_NOTBUILT).  The
+ * accumulator, the frame counter, crh_stats, the selection and read-backs in flight are not touched. */
+CRH_API int crh_read_denoised(crh_ctx* ctx, float* rgba_out /* W*H*4 */);
+/* Micro-benchmark (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): device time of the guide kernel and of every pass of the
+ * parameters in force (the defaults while off) over the current accumulator, each launched `repeats` times between two HIP events on the context's stream, in
+ * milliseconds per launch; pass k reads what pass k - 1 left, as in a read-out.  pass_ms: 5 floats, those beyond `levels` are 0; guide_ms may be NULL.
+ * Synchronous; changes nothing a read-out could see.  Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_bench_denoise(crh_ctx* ctx, uint32_t repeats, float* guide_ms, float* pass_ms /* 5 */);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): all passes of the rule above over
+ * caller-supplied planes -- rgba as crh_save_accum returns it, the id planes as crh_read_ids returns them, table as crh_outline_table_host returns it (may be NULL
+ * with n_tri == 0: then only pixels of one triangle mix) -- the same function the kernel compiles, in a plain loop, one thread.  A triangle index outside [0, n_tri)
+ * has no normal.  width, height >= 1; p checked as crh_set_denoise checks it; rgba_out must not overlap rgba; anything else CRH_E_INVALID. */
+CRH_API int crh_denoise_host(const float* rgba, const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height,
+                             const void* table, uint32_t n_tri, const crh_denoise_params* p, float* rgba_out /* width*height*4 */);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
