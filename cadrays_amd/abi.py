@@ -114,6 +114,17 @@ class crh_denoise_params(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("normal_cos", C.c_float), ("depth_ratio", C.c_float), ("until_samples", C.c_uint32)]
 
 
+class crh_reproject_params(C.Structure):
+    """the reprojected display history's parameters (include/cadrays_hip.h; crh_reproject_defaults fills them: REPROJECT_DEFAULTS below)"""
+    _fields_ = [("max_history", C.c_float), ("until_samples", C.c_uint32), ("normal_cos", C.c_float), ("depth_ratio", C.c_float)]
+
+
+class crh_reproject_frame(C.Structure):
+    """the camera frame of the view a display history was taken from (include/cadrays_hip.h; crh_reproject_frame_host derives it from a camera)"""
+    _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("fwd", C.c_float * 3), ("tan_half", C.c_float), ("aspect", C.c_float),
+                ("ortho_scale", C.c_float), ("is_ortho", C.c_uint32)]
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -124,7 +135,10 @@ OUTLINE_DEFAULTS = dict(kinds=OUTLINE_ALL, crease_cos=_f32(0.8660254037844387), 
 
 DENOISE_DEFAULTS = dict(levels=4, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05), until_samples=256)      # cos 25 deg
 
+REPROJECT_DEFAULTS = dict(max_history=16.0, until_samples=64, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05))      # cos 25 deg
+
 assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
+assert C.sizeof(crh_reproject_params) == 16 and C.sizeof(crh_reproject_frame) == 64
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_region_stats) == 32
@@ -148,4 +162,5 @@ EXPORTS = [
     "crh_query_region", "crh_region_stats_host", "crh_region_select",
     "crh_outline_defaults", "crh_set_outline", "crh_get_outline", "crh_read_outline", "crh_outline_table_host", "crh_outline_mask_host", "crh_outline_draw_host",
     "crh_denoise_defaults", "crh_set_denoise", "crh_get_denoise", "crh_read_denoised", "crh_denoise_host", "crh_bench_denoise",
+    "crh_reproject_defaults", "crh_set_reproject", "crh_get_reproject", "crh_read_reprojected", "crh_bench_reproject", "crh_reproject_frame_host", "crh_reproject_host",
 ]

@@ -96,6 +96,15 @@ def denoise_params(**fields):
     return abi.crh_denoise_params(int(v["levels"]), float(v["normal_cos"]), float(v["depth_ratio"]), int(v["until_samples"]))
 
 
+def reproject_params(**fields):
+    """abi.crh_reproject_params: the defaults (abi.REPROJECT_DEFAULTS == crh_reproject_defaults) with the named fields replaced; an unknown name is an error"""
+    unknown = sorted(set(fields) - set(abi.REPROJECT_DEFAULTS))
+    if unknown:
+        raise ValueError(f"no such reproject parameter {unknown}; crh_reproject_params has {sorted(abi.REPROJECT_DEFAULTS)}")
+    v = dict(abi.REPROJECT_DEFAULTS); v.update(fields)
+    return abi.crh_reproject_params(float(v["max_history"]), int(v["until_samples"]), float(v["normal_cos"]), float(v["depth_ratio"]))
+
+
 class Backend:
     """One rendering context ( == one V3d_View on one GPU )."""
 
@@ -501,6 +510,35 @@ class Backend:
         g, p = C.c_float(0), (C.c_float * 5)()
         self._call("bench_denoise", C.c_uint32(int(repeats)), C.byref(g), p)
         return {"guide_ms": float(g.value), "pass_ms": [float(x) for x in p]}
+
+    # -- reprojected display history in front of the denoise filter (crh_reproject.cpp) ------
+    def set_reproject(self, on=True, **params):
+        """crh_set_reproject: set_camera keeps what the ending view displayed, and every LDR read-out of the next view blends it in through the first-hit points
+        (fields of crh_reproject_params by name, the others take crh_reproject_defaults); on=False / None switches it off and drops the history.  Display state."""
+        if not on:
+            self._call("set_reproject", None)
+            return
+        p = reproject_params(**params)
+        self._call("set_reproject", C.byref(p))
+
+    def get_reproject(self):
+        """crh_get_reproject: dict(max_history, until_samples, normal_cos, depth_ratio, on, history_valid) as in force (the defaults while the feature is off)"""
+        p, on, valid = abi.crh_reproject_params(), C.c_int(0), C.c_int(0)
+        self._call("get_reproject", C.byref(p), C.byref(on), C.byref(valid))
+        return {"max_history": np.float32(p.max_history), "until_samples": int(p.until_samples), "normal_cos": np.float32(p.normal_cos),
+                "depth_ratio": np.float32(p.depth_ratio), "on": bool(on.value), "history_valid": bool(valid.value)}
+
+    def read_reprojected(self):
+        """crh_read_reprojected: (H, W, 4) float32 (r, g, b, w), the image the denoise filter / the tone map of a read_ldr issued now would receive"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._call("read_reprojected", _fp(out))
+        return out
+
+    def bench_reproject(self, repeats=20):
+        """crh_bench_reproject: dict(resolve_ms, capture_ms) -- device time per launch of a read-out's resolve kernel and of what a capture enqueues (HIP events)"""
+        r, k = C.c_float(0), C.c_float(0)
+        self._call("bench_reproject", C.c_uint32(int(repeats)), C.byref(r), C.byref(k))
+        return {"resolve_ms": float(r.value), "capture_ms": float(k.value)}
 
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):

@@ -131,6 +131,7 @@ int do_reset(crh_ctx* c)
 {
   // stream-ordered: kernels still in flight finish into the old accumulator contents first, nothing is waited for
   CRH_HIP(hipSetDevice(c->device));
+  reproject_restart(c);                                  // the display history survives a crh_reset that follows its capture, nothing else (crh_reproject.cpp)
   int rc = alloc_accum(c); if (rc) return rc;
   // A restart touches the ACCUMULATOR, not what a frame's tracing reads: the frame pipeline (render_impl) lets the first frame of the new accumulation trace while
   // the last frames of the old one finish -- its accumulate waits for reset_ev, its counters go to the next block of the ring (zeroed one restart ago).
@@ -290,7 +291,7 @@ void crh_destroy(crh_ctx* c)
 
 const char* crh_last_error(crh_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
-int crh_reset(crh_ctx* c) { if (!c) return CRH_E_INVALID; return do_reset(c); }
+int crh_reset(crh_ctx* c) { if (!c) return CRH_E_INVALID; c->rp_from_reset = true; return do_reset(c); }
 
 int crh_sync(crh_ctx* c) { if (!c) return CRH_E_INVALID; c->read_since_render = true; CRH_HIP(hipSetDevice(c->device)); CRH_HIP(hipStreamSynchronize(cstream(c))); return check_device_error(c); }
 

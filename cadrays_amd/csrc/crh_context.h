@@ -15,6 +15,8 @@
 //   crh_region.cpp     region queries on the id buffer: rectangle / lasso selection, visible objects (region_kernels.hip), the host-only twin
 //   crh_outline.cpp    feature lines on the LDR read-out: object, depth and crease edges from the id buffer (outline_kernels.hip), the host-only twins
 //   crh_denoise.cpp    the denoised display: an id-guided a-trous filter in front of the LDR read-outs' tone map (denoise_kernels.hip), the host-only twin
+//   crh_reproject.cpp  reprojected display history: the image an ending view displayed, blended into the next view's in front of the denoise filter
+//                      (reproject_kernels.hip), the capture in crh_set_camera, the host-only twin
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
@@ -285,6 +287,21 @@ struct DenoiseState {
   bool dn_staged = true;            // steps 1 and 2 take the LDS-staged kernel (denoise_kernels.hip): 67 - 72 against 77 - 85 us per pass at 1080p; CRH_DENOISE_STAGED=0: the plain gather; the same bytes either way
 };
 
+// ---- reprojected display history (crh_reproject.cpp): display state like the denoised display -- only the LDR read-outs (and crh_read_reprojected) look at it.  The
+// HISTORY is what crh_set_camera captured of the view that ended: two images (a capture reads one and writes the other), a copy of that view's guide planes, its camera
+// frame.  One output image per SET, as the denoise filter has them: set 0 the context's stream, set 1 the read-back stream.  A host that never switches the feature on
+// pays nothing.
+struct ReprojectState {
+  bool rp_on = false; crh_reproject_params rp_par{};
+  DevBuf<float4> d_rp_hist[2]; uint32_t rp_cur = 0;                   // rp_cur: the image that holds the valid history
+  DevBuf<float4> d_rp_hguide; DevBuf<int2> d_rp_hids; crh_reproject_frame rp_frame{}; uint32_t rp_w = 0, rp_h = 0;
+  bool rp_valid = false;          // a history exists (for the frame size rp_w x rp_h)
+  bool rp_fresh = false;          // ... and was captured since the last restart: the crh_reset that follows keeps it
+  bool rp_captured = false;       // a capture has been made since the last restart
+  bool rp_from_reset = false;     // do_reset is being reached through crh_reset
+  DevBuf<float4> d_rp_out[2];
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -295,7 +312,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ReprojectState, crh::TimingState {
   int device = 0;
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
@@ -390,6 +407,21 @@ int ensure_outline_table(crh_ctx* c);                              // the per-tr
 // else the filtered image of scratch set `set` (0: the context's stream, 1: the read-back stream), its passes enqueued on `on`.  Called just BEFORE launch_tonemap,
 // after the metering, which keeps reading `src`.
 int denoise_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown);
+int ensure_guide(crh_ctx* c);      // the guide (d_dn_guide, d_dn_ids) of the state in force, computed if stale; synchronous on the side stream
+// ---- crh_reproject.cpp
+// The image the denoise filter / the tone map of an LDR read-out receives, in *shown: `src` itself while the feature is off, there is no scene or no valid history
+// (nothing is allocated, nothing is launched), else the resolved image of set `set` (0: the context's stream, 1: the read-back stream), enqueued on `on`.  Called just
+// BEFORE denoise_src, after the metering, which keeps reading `src`.
+int reproject_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown);
+int reproject_capture(crh_ctx* c, const crh_camera* next);      // crh_set_camera, BEFORE `next` replaces the camera in force: the header's LIFE CYCLE
+// do_reset: a restart reached through crh_reset keeps a fresh history, any other drops it; either way a new capture may follow
+inline void reproject_restart(crh_ctx* c)
+{
+  const bool keep = c->rp_from_reset && c->rp_fresh;
+  c->rp_from_reset = c->rp_fresh = c->rp_captured = false;
+  if (!keep) c->rp_valid = false;
+}
+inline void reproject_drop(crh_ctx* c) { c->rp_valid = c->rp_fresh = false; }      // the setters that change the picture without a restart of their own
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

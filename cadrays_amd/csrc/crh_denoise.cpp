@@ -31,25 +31,6 @@ const char* params_refused(const crh_denoise_params* p)
 
 DenoiseRule rule_of(const crh_denoise_params& p) { return DenoiseRule{p.levels, p.normal_cos, p.depth_ratio, (float)p.until_samples}; }      // (2^20 is exact)
 
-// The guide of the state in force, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids and the outline mask are).
-int ensure_guide(crh_ctx* c)
-{
-  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
-  CRH_HIP(hipSetDevice(c->device));
-  if ((rc = pick_stream(c))) return rc;
-  if ((rc = ensure_outline_table(c))) return rc;
-  const uint32_t W = c->par.width, H = c->par.height;
-  if (c->dn_guide_valid && c->dn_guide_ids_gen == c->ids_gen && c->dn_guide_table_gen == c->ol_table_gen && c->dn_guide_w == W && c->dn_guide_h == H) return CRH_OK;
-  if ((rc = wait_overlay_readers(c))) return rc;         // an asynchronous read-back may still be filtering from the guide
-  c->dn_guide_valid = false;
-  CRH_HIP(c->d_dn_guide.reserve((size_t)W * H)); CRH_HIP(c->d_dn_ids.reserve((size_t)W * H));      // (what read the old blocks has been waited for: the synchronous
-  launch_denoise_guide(c->pk_stream, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids);      //  read-outs end with a wait, the readers just above)
-  CRH_HIP(hipGetLastError());
-  CRH_HIP(hipStreamSynchronize(c->pk_stream));
-  c->dn_guide_valid = true; c->dn_guide_ids_gen = c->ids_gen; c->dn_guide_table_gen = c->ol_table_gen; c->dn_guide_w = W; c->dn_guide_h = H;
-  return CRH_OK;
-}
-
 // The passes of rule R from `src` through the two images of scratch set `set`, enqueued on `on`; *shown = the image the last pass wrote.
 int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const DenoiseRule& R, const float4** shown)
 {
@@ -77,6 +58,25 @@ int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const Denoise
 
 namespace crh {
 namespace api {
+
+// The guide of the state in force, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids and the outline mask are).
+int ensure_guide(crh_ctx* c)
+{
+  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
+  CRH_HIP(hipSetDevice(c->device));
+  if ((rc = pick_stream(c))) return rc;
+  if ((rc = ensure_outline_table(c))) return rc;
+  const uint32_t W = c->par.width, H = c->par.height;
+  if (c->dn_guide_valid && c->dn_guide_ids_gen == c->ids_gen && c->dn_guide_table_gen == c->ol_table_gen && c->dn_guide_w == W && c->dn_guide_h == H) return CRH_OK;
+  if ((rc = wait_overlay_readers(c))) return rc;         // an asynchronous read-back may still be filtering from the guide
+  c->dn_guide_valid = false;
+  CRH_HIP(c->d_dn_guide.reserve((size_t)W * H)); CRH_HIP(c->d_dn_ids.reserve((size_t)W * H));      // (what read the old blocks has been waited for: the synchronous
+  launch_denoise_guide(c->pk_stream, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids);      //  read-outs end with a wait, the readers just above)
+  CRH_HIP(hipGetLastError());
+  CRH_HIP(hipStreamSynchronize(c->pk_stream));
+  c->dn_guide_valid = true; c->dn_guide_ids_gen = c->ids_gen; c->dn_guide_table_gen = c->ol_table_gen; c->dn_guide_w = W; c->dn_guide_h = H;
+  return CRH_OK;
+}
 
 // Called by the LDR read-outs between the metering and the tone map, on the stream the tone map runs on.  Feature off or no scene: nothing is allocated, nothing is
 // launched -- the tone map reads `src`.
@@ -131,7 +131,8 @@ int crh_read_denoised(crh_ctx* c, float* rgba_out)
   CRH_HIP(hipSetDevice(c->device));
   const float4* shown = nullptr;
   hipStream_t on = cstream(c);
-  if (int rc = filter(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, rule_of(p), &shown)) return rc;
+  if (int rc = reproject_src(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, &shown)) return rc;      // what a read-out's filter receives (crh_reproject.cpp): the accumulator itself while that feature is off
+  if (int rc = filter(c, on, shown, 0, rule_of(p), &shown)) return rc;
   CRH_HIP(hipMemcpyAsync(rgba_out, shown, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, on));
   CRH_HIP(hipStreamSynchronize(on));
   return CRH_OK;

@@ -69,7 +69,8 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
   const float* metered = meter_in_front(c, L, src, 0);               // auto exposure meters the UNFILTERED image ...
   const float4* shown;
-  if (int rc = denoise_src(c, L.stream, src, 0, &shown)) return rc;   // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
+  if (int rc = reproject_src(c, L.stream, src, 0, &shown)) return rc; // ... reprojected display history (crh_reproject.cpp) and ...
+  if (int rc = denoise_src(c, L.stream, shown, 0, &shown)) return rc; // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
   launch_tonemap(L, shown, c->d_scratch.as<uint8_t>(), n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, metered);
   if (int rc = outline_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // feature lines (crh_outline.cpp): nothing at all while the feature is off
   if (int rc = overlay_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
@@ -113,7 +114,8 @@ static int read_begin(crh_ctx* c, bool hdr)
     const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
     const float* metered = meter_in_front(c, L, src, 1 + (int)slot);
     const float4* shown;
-    if (int rc = denoise_src(c, c->rb_stream, src, 1, &shown)) return rc;      // the denoised display (crh_denoise.cpp); rb_tm below covers its read of the accumulator
+    if (int rc = reproject_src(c, c->rb_stream, src, 1, &shown)) return rc;     // reprojected display history (crh_reproject.cpp); rb_tm below covers its reads too
+    if (int rc = denoise_src(c, c->rb_stream, shown, 1, &shown)) return rc;      // the denoised display (crh_denoise.cpp); rb_tm below covers its read of the accumulator
     launch_tonemap(L, shown, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, metered);
     if (int rc = outline_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // feature lines (crh_outline.cpp)
     if (int rc = overlay_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // hover / selection (crh_pick.cpp)
@@ -237,7 +239,7 @@ int crh_load_accum(crh_ctx* c, const float* in, uint32_t frames_done)
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   CRH_HIP(hipMemcpyAsync(c->d_accum, in, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyHostToDevice, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
-  c->frames_done = frames_done; c->pending_n = 0; c->assembled_valid = false;
+  c->frames_done = frames_done; c->pending_n = 0; c->assembled_valid = false; reproject_drop(c);
   return CRH_OK;
 }
 

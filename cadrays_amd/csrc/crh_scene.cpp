@@ -469,7 +469,7 @@ int crh_set_materials(crh_ctx* c, const crh_bsdf* m, uint32_t n)
   if (!c || (n && !m)) return fail(c, CRH_E_INVALID, "null materials");
   if (!all_finite((const float*)m, 32 * (size_t)n)) return fail(c, CRH_E_INVALID, "material holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
-  c->mats.assign(m, m + n); c->pending_n = 0;
+  c->mats.assign(m, m + n); c->pending_n = 0; reproject_drop(c);
   return dev_put(c, c->d_mats, c->mats.data(), sizeof(crh_bsdf) * n, 16 * sizeof(crh_bsdf));
 }
 
@@ -478,7 +478,7 @@ int crh_set_lights(crh_ctx* c, const crh_light* l, uint32_t n)
   if (!c || (n && !l)) return fail(c, CRH_E_INVALID, "null lights");
   if (!all_finite((const float*)l, 8 * (size_t)n, 1.0e30f)) return fail(c, CRH_E_INVALID, "light holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
-  c->lights.assign(l, l + n); c->pending_n = 0;
+  c->lights.assign(l, l + n); c->pending_n = 0; reproject_drop(c);
   return upload_lights(c);
 }
 
@@ -487,7 +487,7 @@ int crh_set_envmap(crh_ctx* c, const float* rgb, uint32_t w, uint32_t h)
   if (!c) return CRH_E_INVALID;
   if (rgb && w && h && !all_finite(rgb, 3 * (size_t)w * h)) return fail(c, CRH_E_INVALID, "environment map holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
-  c->envW = c->envH = 0; c->pending_n = 0;
+  c->envW = c->envH = 0; c->pending_n = 0; reproject_drop(c);
   if (rgb && w && h) {
     std::vector<float> t(4 * (size_t)w * h);
     for (size_t i = 0; i < (size_t)w * h; ++i) { t[4 * i] = rgb[3 * i]; t[4 * i + 1] = rgb[3 * i + 1]; t[4 * i + 2] = rgb[3 * i + 2]; t[4 * i + 3] = 0.f; }
@@ -525,6 +525,7 @@ int crh_set_camera(crh_ctx* c, const crh_camera* cam)
   const float f[] = {cam->eye[0], cam->eye[1], cam->eye[2], cam->dir[0], cam->dir[1], cam->dir[2], cam->up[0], cam->up[1], cam->up[2],
                      cam->fovy_deg, cam->aspect, cam->ortho_scale, cam->aperture_radius, cam->focal_dist};
   if (!all_finite(f, sizeof f / sizeof f[0], 1.0e30f)) return fail(c, CRH_E_INVALID, "camera holds a NaN / Inf");
+  if (int rc = reproject_capture(c, cam)) return rc;    // the display history (crh_reproject.cpp): nothing at all while the feature is off
   c->cam = *cam; c->pending_n = 0;                      // samples traced ahead with the old camera are dropped
   c->ids_valid = false;                                 // ... and so is the first-hit id buffer (crh_pick.cpp)
   c->read_since_render = true;

@@ -6,27 +6,7 @@
 //   k_overlay            outline / interior tint of the selected and the hovered objects over the tone-mapped bytes
 // Nothing here draws from the RNG or touches path state, queues, the accumulator or the counters of crh_stats.
 
-// The camera ray camera_ray() (k_raygen.h) produces with jitter (0.5, 0.5) and no lens sample, restated: camera_ray() seeds and advances the RNG on its way, and the
-// rendered images must not depend on how the compiler schedules a shared helper.  Same operations in the same order for the three camera models.
-__host__ __device__ __forceinline__ void pixel_centre_ray(const DScene& S, const uint32_t px, const uint32_t py, v3& o, v3& d)
-{
-  const float jx = 0.5f, jy = 0.5f;
-  const float nx = CRH_FMA(((float)px + jx) / (float)S.width, 2.0f, -1.0f);
-  const float ny = CRH_FMA(((float)py + jy) / (float)S.height, -2.0f, 1.0f);
-  if (S.is_ortho) {
-    const float sx = (nx * S.ortho_scale) * S.aspect, sy = ny * S.ortho_scale;
-    o = crh_madd3(crh_madd3(S.eye, S.right, sx), S.up, sy);
-    d = S.fwd;
-  } else if (S.spec_raygen) {
-    const float u = ((float)px + jx) / (float)S.width, v = 1.0f - ((float)py + jy) / (float)S.height;
-    o = S.eye;
-    d = crh_norm3(crh_lerp3(crh_lerp3(S.corner[0], S.corner[1], u), crh_lerp3(S.corner[2], S.corner[3], u), v));
-  } else {
-    const float sx = (nx * S.tan_half) * S.aspect, sy = ny * S.tan_half;
-    o = S.eye;
-    d = crh_norm3(crh_madd3(crh_madd3(S.fwd, S.right, sx), S.up, sy));
-  }
-}
+#include "k_pixel_ray.h"      // pixel_centre_ray: the pixel-centre camera ray, shared with reproject_kernels.hip
 
 // Ray slot <-> pixel of the id pass: 8x8-pixel blocks, row-major over ceil(W/8) x ceil(H/8), so that one wavefront of the traversal kernel owns one block
 // (slot_pixel's mapping inside a tile, without the tiles: the id buffer is never sharded).  Slots of a partial block that fall outside the image repeat the

@@ -176,6 +176,22 @@ class View(Backend):
         """(H, W, 4) float32: the image the tone map of an LDR read-out issued now would read, with the parameters in force (the defaults while off)"""
         return self.read_denoised()
 
+    # ---- reprojected display history (crh_reproject.cpp; no counterpart in the reference: OCCT's path tracer shows the raw accumulation) ----
+    def SetReproject(self, max_history=16.0, until_samples=64, normal_deg=25.0, depth_rel=0.05):
+        """keep the picture through a camera move: set_camera + reset from now on carry what the ending view displayed over to the next one, blended in with weight up
+        to max_history samples until a pixel has until_samples of its own.  Nothing restarts.  The angle and the step become normal_cos / depth_ratio in double,
+        rounded once."""
+        self.set_reproject(True, max_history=float(max_history), until_samples=int(until_samples), normal_cos=outline_crease_cos(normal_deg),
+                           depth_ratio=outline_depth_ratio(depth_rel))
+
+    def ClearReproject(self):
+        """no history: the LDR bytes of a view that never called SetReproject"""
+        self.set_reproject(False)
+
+    def ReadReprojected(self):
+        """(H, W, 4) float32: the image the denoise filter / the tone map of an LDR read-out issued now would receive"""
+        return self.read_reprojected()
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -487,6 +503,53 @@ def denoise_host(rgba, object_px, triangle_px, t_px, table, **params):
                               C.c_uint32(len(tb)), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc != 0:
         raise BackendError(f"crh_denoise_host -> {rc}")
+    return out
+
+
+def reproject_frame_host(cam, width, height):
+    """crh_reproject_frame_host on the host only (no GPU): the camera frame of a scenes.Camera at a frame size, as a dict of float32 arrays / scalars
+    (eye, right, up, fwd, tan_half, aspect, ortho_scale, is_ortho)"""
+    from .binding import camera_struct
+    lib = load_library()
+    F = abi.crh_reproject_frame()
+    rc = lib.crh_reproject_frame_host(C.byref(camera_struct(cam)), C.c_uint32(int(width)), C.c_uint32(int(height)), C.byref(F))
+    if rc != 0:
+        raise BackendError(f"crh_reproject_frame_host -> {rc}")
+    return dict(eye=np.array(F.eye[:], np.float32), right=np.array(F.right[:], np.float32), up=np.array(F.up[:], np.float32), fwd=np.array(F.fwd[:], np.float32),
+                tan_half=np.float32(F.tan_half), aspect=np.float32(F.aspect), ortho_scale=np.float32(F.ortho_scale), is_ortho=int(F.is_ortho))
+
+
+def reproject_host(accum, rays, object_px, triangle_px, t_px, history, table, **params):
+    """crh_reproject_host on the host only (no GPU): accum (H, W, 4) float32 as save_accum returns it; rays (H * W, 8) float32 as camera_rays returns them for the
+    pixels in row-major order; the planes as read_ids returns them; history = None (every pixel passes through) or a dict(rgba, ob, tr, t, frame): the image, the id
+    planes of its view and that view's camera frame as reproject_frame_host returns it; table as outline_table_host returns it (None / empty: only taps of the
+    same triangle count); params as in Backend.set_reproject (fields of crh_reproject_params); the (H, W, 4) float32 image read_reprojected returns"""
+    from .binding import reproject_params
+    lib = load_library()
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    img = np.ascontiguousarray(accum, np.float32)
+    ob, tr, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == tr.shape == t.shape and img.shape == ob.shape + (4,)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    assert len(r) == ob.size
+    tb = np.zeros(0, abi.OUTLINE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.OUTLINE_TABLE_DTYPE)
+    h = [None] * 5
+    if history is not None:
+        himg = np.ascontiguousarray(history["rgba"], np.float32)
+        hob, htr, ht = np.ascontiguousarray(history["ob"], np.int32), np.ascontiguousarray(history["tr"], np.int32), np.ascontiguousarray(history["t"], np.float32)
+        assert himg.shape == img.shape and hob.shape == htr.shape == ht.shape == ob.shape
+        f = history["frame"]
+        F = abi.crh_reproject_frame()
+        F.eye[:] = [float(x) for x in f["eye"]]; F.right[:] = [float(x) for x in f["right"]]; F.up[:] = [float(x) for x in f["up"]]; F.fwd[:] = [float(x) for x in f["fwd"]]
+        F.tan_half, F.aspect, F.ortho_scale, F.is_ortho = float(f["tan_half"]), float(f["aspect"]), float(f["ortho_scale"]), int(f["is_ortho"])
+        h = [himg.ctypes.data_as(fp), hob.ctypes.data_as(ip), htr.ctypes.data_as(ip), ht.ctypes.data_as(fp), C.byref(F)]
+    p = reproject_params(**params)
+    out = np.zeros(img.shape, np.float32)
+    rc = lib.crh_reproject_host(img.ctypes.data_as(fp), r.ctypes.data_as(fp), ob.ctypes.data_as(ip), tr.ctypes.data_as(ip), t.ctypes.data_as(fp), *h,
+                                tb.ctypes.data_as(C.c_void_p) if len(tb) else None, C.c_uint32(len(tb)), C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]), C.byref(p),
+                                out.ctypes.data_as(fp))
+    if rc != 0:
+        raise BackendError(f"crh_reproject_host -> {rc}")
     return out
 
 

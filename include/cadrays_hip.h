@@ -596,7 +596,7 @@ CRH_API int crh_outline_draw_host(const uint8_t* mask, uint32_t width, uint32_t 
  *                   the frame (nothing wraps), !(a[q].w > 0), any of in[q].rgb is not finite, or !similar(p, q); otherwise c = h[dy + 2] * h[dx + 2], an integer
  *                   in {1, 4, 6, 16, 24, 36} exact as a float, sr = sr + c * in[q].r -- the product rounded, then the sum rounded -- likewise g and b, Wsum += c.
  *     OUTPUT        out[p] = (sr / (float)Wsum, sg / (float)Wsum, sb / (float)Wsum, in[p].w).  The centre always counts: Wsum >= 36.  The division is the plain a / b.
- *   BINARY edge-stopping weights, INTEGER spline weights; no exp, no fused multiply-add, no atomic, no variance estimate, no temporal reprojection.  Every pixel GATHERS:
+ *   BINARY edge-stopping weights, INTEGER spline weights; no exp, no fused multiply-add, no atomic, no variance estimate, nothing temporal (reprojection is the next section's, in front of this filter).  Every pixel GATHERS:
  *   nothing is scattered and nothing depends on the order of arrival, so the device, the host twin and a numpy restatement agree bit for bit.
  *   KNOWN LIMITS: diffuse textures are smoothed until the thresholds pass (there is no albedo demodulation); a surface at a grazing angle filters less along the view
  *   direction (the depth test is a ratio of ray distances, as in the feature lines); an unwelded faceted mesh filters per facet only when normal_cos excludes its
@@ -634,6 +634,94 @@ CRH_API int crh_bench_denoise(crh_ctx* ctx, uint32_t repeats, float* guide_ms, f
  * has no normal.  width, height >= 1; p checked as crh_set_denoise checks it; rgba_out must not overlap rgba; anything else CRH_E_INVALID. */
 CRH_API int crh_denoise_host(const float* rgba, const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height,
                              const void* table, uint32_t n_tri, const crh_denoise_params* p, float* rgba_out /* width*height*4 */);
+
+/* --- reprojected display history (crh_reproject.cpp, cadrays_amd/csrc/reproject_kernels.hip) ------------------------------------------------------
+ * The application restarts the accumulation on every camera change (AppViewer.cxx:979-984), so during a drag every displayed image has one sample.  With this
+ * feature on, crh_set_camera keeps the image the ending view DISPLAYED (its accumulator blended with its own history), that view's guide and its camera frame;
+ * the LDR read-outs of the next view fetch it through the first-hit point of every pixel and blend it with the new accumulator: ten frames of a drag are about
+ * ten samples per pixel wherever the surface was in view before.  The reference has NO counterpart: OCCT's path tracer shows the raw accumulation.  Display state
+ * like crh_set_denoise: ONLY the image the denoise filter / the tone map reads changes.  Read-out order: metering (unfiltered accumulator), REPROJECTION, denoise
+ * filter, tone map, ShowSamplingTiles outline, feature lines, selection, hover.  out.w = a.w + hn, so the filter's level thresholds see the history's samples and
+ * back off by themselves.  crh_read_hdr*, crh_save_accum, crh_reduce, crh_accum_device_ptr, the tile statistics, the id buffer, crh_stats and the frame counter
+ * never see the feature.  Off or never set: nothing is allocated, nothing is launched, and every byte is that of a context that never heard of it.
+ *   ARITHMETIC: plain float32, one operation at a time, each rounded; NO fused multiply-add anywhere; a / b and sqrtf are the IEEE ones.
+ *   INPUTS per pixel p = (px, py) of the current view: a[p] = (r, g, b, w), the image the tone map would read without the feature (the assembled frame of crh_reduce
+ *   while it is valid, else the accumulator); the guide g1[p] = {object, triangle, t, n, has_n} exactly as the denoised display defines it; (o, d), the pixel-centre
+ *   ray, bitwise what crh_camera_rays returns for p.
+ *   HISTORY, taken from an earlier view of the same frame size: an image h[q] = (r, g, b, n), n > 0 an effective sample count, n == 0 none; the guide g0[q] of that
+ *   view; that view's camera frame (crh_reproject_frame: eye0, right0, up0, fwd0, tan_half0, aspect0, ortho_scale0, is_ortho0, derived as the kernels' scene record
+ *   derives them: fwd = unit dir, right = unit (fwd x up), up = right x fwd, tan_half = sin / cos of half the field of view, aspect <= 0 -> width / height).
+ *   PASS-THROUGH  out[p] = a[p], all four floats bitwise, when any of: there is no valid history; g1.triangle[p] < 0 (background and environment map stay the
+ *                 accumulator's); any of a[p].rgb is NaN or +-Inf; a[p].w >= (float)until_samples -- from that count on the displayed image is what it would be
+ *                 without the feature, to the bit.  Every "no history" below is this pass-through too.
+ *   PROJECT       P.k = o.k + t * d.k (the product rounded, then the sum); q = P - eye0; x = (q.x r.x + q.y r.y) + q.z r.z with r = right0, y likewise with up0,
+ *                 z with fwd0.  Perspective: no history unless z > 0; den = z * tan_half0; ny = y / den; nx = x / (den * aspect0); the expected old distance
+ *                 te = sqrtf((q.x q.x + q.y q.y) + q.z q.z).  Orthographic: ny = y / ortho_scale0; nx = x / (ortho_scale0 * aspect0); te = z; no history unless
+ *                 te > 0.  fx = (nx + 1.0f) * (0.5f * (float)W) - 0.5f; fy = (1.0f - ny) * (0.5f * (float)H) - 0.5f.  No history unless both are finite,
+ *                 -1 < fx < W and -1 < fy < H.  x0 = floorf(fx), ax = fx - x0; y0 = floorf(fy), ay = fy - y0.
+ *   GATHER        taps j = 0..3 at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with weights (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay: the factors
+ *                 rounded, then the product.  A tap counts iff it lies in the frame (nothing wraps), h[q].n > 0, h[q].rgb is finite, its weight is > 0 and
+ *                 match(p, q): g0.object[q] == g1.object[p]; g0.triangle[q] >= 0; and either g0.triangle[q] == g1.triangle[p], or has_n of both,
+ *                 fabsf((n.x m.x + n.y m.y) + n.z m.z) >= normal_cos, and not hi > lo * depth_ratio with lo / hi the smaller / larger of te and g0.t[q] (one
+ *                 rounded product, then a strict compare).  S, sc.rgb, sn start at 0.0f and take S = S + w_j, sc = sc + w_j * h.rgb, sn = sn + w_j * h.n for the
+ *                 taps that count, in tap order, every product and every sum rounded.  No history when no tap counted.  hc = sc / S; hn = fminf(sn / S, max_history).
+ *   BLEND         a.w > 0: W2 = a.w + hn, out = ((a.r * a.w + hc.r * hn) / W2, likewise g and b, W2).  !(a.w > 0) -- a tile not sampled yet --: out = (hc, hn).
+ *   Every pixel GATHERS: no atomic, nothing depends on the order of arrival, so the device, the host twin and a numpy restatement agree bit for bit.
+ *   LIFE CYCLE    crh_set_camera CAPTURES, before the new camera replaces the old one, when all of: the feature is on; the scene is built; the new camera differs
+ *                 bitwise from the one in force; no capture has been made since the last restart; crh_spec.raygen_bilinear == 0; frames_done > 0 or a valid
+ *                 history exists.  The capture enqueues on the context's stream, behind the frames in flight and in front of crh_reset's clears: the rule above over
+ *                 the ending view into the other of two history images, a copy of that view's guide, its camera frame.  Nothing waits on the host except the guide
+ *                 of a view that was never displayed, and read-backs in flight that still read what is overwritten.  A capture marks the history FRESH.  A restart
+ *                 reached through crh_reset keeps a fresh history and clears the mark; a restart reached any other way (geometry, crh_build, transforms, visibility,
+ *                 crh_add_object, textures, crh_set_params, crh_set_spec), a crh_reset without a capture in front of it, crh_set_materials, crh_set_lights,
+ *                 crh_set_envmap, crh_load_accum, a change of the frame size and crh_set_reproject(NULL) DROP it.  The history is recursive -- what is captured is the
+ *                 resolved image -- so it survives a whole drag with weight up to max_history.  Host sequence: crh_set_camera, then crh_reset; the
+ *                 reverse order simply gets no history.  With crh_spec.raygen_bilinear != 0 the feature NEVER captures (the projection above inverts the
+ *                 tan_half ray, not the bilinear one).
+ *   KNOWN LIMITS: view-dependent shading -- glossy, glass, a light in view -- lags by up to max_history samples until until_samples is reached; repeated bilinear
+ *   resampling softens a long drag; depth of field is reprojected through the pixel-centre pinhole ray. */
+typedef struct crh_reproject_params {
+  float    max_history;    /* 1..1024: cap of the history's effective sample count; default 16                          */
+  uint32_t until_samples;  /* 1..2^20: a pixel with a.w >= until_samples is passed through; default 64                   */
+  float    normal_cos;     /* in (0, 1]: another triangle's tap counts iff |n . m| >= normal_cos; default cos 25 deg     */
+  float    depth_ratio;    /* >= 1, finite: ... and not max(te, t0) > min(te, t0) * depth_ratio; default 1.05            */
+} crh_reproject_params;    /* 16 B */
+typedef struct crh_reproject_frame {
+  float    eye[3], right[3], up[3], fwd[3];
+  float    tan_half, aspect, ortho_scale;
+  uint32_t is_ortho;
+} crh_reproject_frame;     /* 64 B: the camera frame of the view a history was taken from */
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  16, 64, cos 25 deg, 1.05 */
+CRH_API void crh_reproject_defaults(crh_reproject_params* p);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  Switch the feature on with these parameters, or off with NULL -- the state of a
+ * new context; NULL drops the history.  Display state: no restart, no work on any stream, allowed before crh_build.  CRH_E_INVALID with a message: max_history
+ * outside 1..1024, until_samples outside 1..2^20, normal_cos outside (0, 1], depth_ratio below 1, a NaN or Inf anywhere.  Changing the parameters keeps the history. */
+CRH_API int crh_set_reproject(crh_ctx* ctx, const crh_reproject_params* p /* NULL = off */);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The parameters in force (the defaults while the feature is off), whether it is
+ * on, and whether a history is valid for the frame size in force; every pointer may be NULL. */
+CRH_API int crh_get_reproject(crh_ctx* ctx, crh_reproject_params* out, int* on, int* history_valid);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The image the denoise filter or the tone map of a read-out issued now would
+ * receive, W*H*4 floats (r, g, b, w), row 0 = top: the rule above with the parameters in force; the accumulator itself while the feature is off or no history is
+ * valid.  Synchronous; runs on the context's stream, ordered after everything submitted; a stale id buffer or table is computed first.  Needs a built scene
+ * (CRH_E_NOTBUILT).  Touches nothing a read-out could see: the history, the accumulator, the frame counter, crh_stats and read-backs in flight stay what they are. */
+CRH_API int crh_read_reprojected(crh_ctx* ctx, float* rgba_out /* W*H*4 */);
+/* Micro-benchmark (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): device time of the resolve kernel of a read-out and of what a
+ * capture enqueues (the resolve into a history image and the copy of the guide), each `repeats` times between two HIP events on the context's stream, in
+ * milliseconds per launch.  Without a valid history the current view stands in for it (the identity reprojection: every hit pixel gathers four taps); the history
+ * a read-out could see is not touched.  Either output may be NULL.  Synchronous.  Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_bench_reproject(crh_ctx* ctx, uint32_t repeats, float* resolve_ms, float* capture_ms);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): the camera frame the rule takes, from a
+ * camera and the frame size, derived as the kernels' scene record derives it. */
+CRH_API int crh_reproject_frame_host(const crh_camera* cam, uint32_t width, uint32_t height, crh_reproject_frame* out);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): the rule above over caller-supplied planes --
+ * accum_rgba as crh_save_accum returns it; rays_px 8 floats per pixel in crh_camera_rays' layout {o.xyz, tmax, d.xyz, -}, row-major; the id planes of the current
+ * view as crh_read_ids returns them; hist_rgba (NULL: no valid history, every pixel passes through; the other hist_* are then not read), the id planes of the
+ * history's view and its camera frame; table as crh_outline_table_host returns it (may be NULL with n_tri == 0: then only taps of the same triangle count) -- the same
+ * function the kernel compiles, in a plain loop, one thread.  width, height >= 1; p checked as crh_set_reproject checks it; rgba_out must not overlap an input;
+ * anything else CRH_E_INVALID. */
+CRH_API int crh_reproject_host(const float* accum_rgba, const float* rays_px, const int32_t* object_px, const int32_t* triangle_px, const float* t_px,
+                               const float* hist_rgba, const int32_t* hist_object, const int32_t* hist_triangle, const float* hist_t, const crh_reproject_frame* hist_cam,
+                               const void* table, uint32_t n_tri, uint32_t width, uint32_t height, const crh_reproject_params* p, float* rgba_out /* width*height*4 */);
 
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
