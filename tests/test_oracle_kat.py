@@ -130,7 +130,7 @@ def test_beer_lambert_slab(orc):
     """index-matched (n = 1) absorbing slab of thickness d between camera and a constant sky:
     transmittance exp(-d * c * (1 - a)) per channel, no reflection, no bending."""
     d, c, a = 0.5, 3.0, np.array([0.8, 0.5, 1.0])
-    p0, n0, t0 = plane(z=0.0, half=1.0)          # small scene: the origin offset (1e-5 * diagonal) stays negligible
+    p0, n0, t0 = plane(z=0.0, half=1.0)          # small scene: the origin offset (1e-5 * diagonal) stays negligible (test_integrator_expectation.py has the large one, offset modelled)
     p1, n1, t1 = plane(z=-d, half=1.0, up=False)
     pos = np.concatenate([p0, p1]); nrm = np.concatenate([n0, n1]); t1 = t1.copy(); t1[:, :3] += 4
     tri = np.concatenate([t0, t1])
