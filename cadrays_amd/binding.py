@@ -37,15 +37,27 @@ def _close_all():
             pass
 
 
+def _params(kind, what, fields):
+    """abi.crh_<kind>_params: the defaults (abi.<KIND>_DEFAULTS == crh_<kind>_defaults) with the named fields replaced, each converted to its ctypes field's type;
+    an unknown name is an error, worded with `what`"""
+    defaults, struct = getattr(abi, f"{kind.upper()}_DEFAULTS"), getattr(abi, f"crh_{kind}_params")
+    unknown = sorted(set(fields) - set(defaults))
+    if unknown:
+        raise ValueError(f"no such {what} parameter {unknown}; crh_{kind}_params has {sorted(defaults)}")
+    v, p = dict(defaults, **fields), struct()
+    for name, ctype in struct._fields_:
+        is_array = hasattr(ctype, "_length_")
+        conv = float if (ctype._type_ if is_array else ctype) is C.c_float else int
+        if is_array:
+            getattr(p, name)[:] = [conv(x) for x in v[name]]
+        else:
+            setattr(p, name, conv(v[name]))
+    return p
+
+
 def meter_params(**fields):
     """abi.crh_meter_params: the defaults (abi.METER_DEFAULTS == crh_meter_defaults) with the named fields replaced; an unknown name is an error"""
-    unknown = sorted(set(fields) - set(abi.METER_DEFAULTS))
-    if unknown:
-        raise ValueError(f"no such metering parameter {unknown}; crh_meter_params has {sorted(abi.METER_DEFAULTS)}")
-    v = dict(abi.METER_DEFAULTS); v.update(fields)
-    p = abi.crh_meter_params(float(v["key_stops"]), float(v["min_stops"]), float(v["max_stops"]), int(v["white_permille"]), float(v["white_min"]), float(v["white_max"]))
-    p.rect[:] = [int(x) for x in v["rect"]]
-    return p
+    return _params("meter", "metering", fields)
 
 
 def camera_struct(cam):
@@ -77,32 +89,17 @@ def region_args(rect, poly):
 
 def outline_params(**fields):
     """abi.crh_outline_params: the defaults (abi.OUTLINE_DEFAULTS == crh_outline_defaults) with the named fields replaced; an unknown name is an error"""
-    unknown = sorted(set(fields) - set(abi.OUTLINE_DEFAULTS))
-    if unknown:
-        raise ValueError(f"no such outline parameter {unknown}; crh_outline_params has {sorted(abi.OUTLINE_DEFAULTS)}")
-    v = dict(abi.OUTLINE_DEFAULTS); v.update(fields)
-    p = abi.crh_outline_params(int(v["kinds"]), float(v["crease_cos"]), float(v["depth_ratio"]), int(v["width"]))
-    p.rgb[:] = [int(x) for x in v["rgb"]]
-    p.alpha = int(v["alpha"])
-    return p
+    return _params("outline", "outline", fields)
 
 
 def denoise_params(**fields):
     """abi.crh_denoise_params: the defaults (abi.DENOISE_DEFAULTS == crh_denoise_defaults) with the named fields replaced; an unknown name is an error"""
-    unknown = sorted(set(fields) - set(abi.DENOISE_DEFAULTS))
-    if unknown:
-        raise ValueError(f"no such denoise parameter {unknown}; crh_denoise_params has {sorted(abi.DENOISE_DEFAULTS)}")
-    v = dict(abi.DENOISE_DEFAULTS); v.update(fields)
-    return abi.crh_denoise_params(int(v["levels"]), float(v["normal_cos"]), float(v["depth_ratio"]), int(v["until_samples"]))
+    return _params("denoise", "denoise", fields)
 
 
 def reproject_params(**fields):
     """abi.crh_reproject_params: the defaults (abi.REPROJECT_DEFAULTS == crh_reproject_defaults) with the named fields replaced; an unknown name is an error"""
-    unknown = sorted(set(fields) - set(abi.REPROJECT_DEFAULTS))
-    if unknown:
-        raise ValueError(f"no such reproject parameter {unknown}; crh_reproject_params has {sorted(abi.REPROJECT_DEFAULTS)}")
-    v = dict(abi.REPROJECT_DEFAULTS); v.update(fields)
-    return abi.crh_reproject_params(float(v["max_history"]), int(v["until_samples"]), float(v["normal_cos"]), float(v["depth_ratio"]))
+    return _params("reproject", "reproject", fields)
 
 
 class Backend:

@@ -8,7 +8,8 @@
 //                      the tile order, the two-sided measurement tally; checked on the CPU by tests/schedule_plan_model.cpp
 //   crh_schedule.cpp   the wavefront schedule: lanes, batches, frame pipelining, look-ahead, adaptive iterations -- asks crh_plan.h, enqueues the HIP work;
 //                      crh_render / crh_render_tiles
-//   crh_readback.cpp   HDR / LDR read-back (synchronous and asynchronous), accumulator checkpoints, statistics and kernel timing
+//   crh_readback.cpp   HDR / LDR read-back (synchronous and asynchronous) and THE DISPLAY CHAIN both LDR read-outs enqueue (metering, reprojection, denoise filter,
+//                      tone map, feature lines, overlay: enqueue_display_chain), accumulator checkpoints, statistics and kernel timing
 //   crh_reduce.cpp     crh_reduce (RCCL over xGMI, or peer copies on one device)
 //   crh_pick.cpp       the first-hit id buffer: camera rays, pick, id read-back, selection / hover state and bounds, the overlay of the LDR read-out
 //   crh_fit.cpp        fit the view to the displayed / chosen objects: vertex extents on the device (fit_kernels.hip), the closed-form rule, the host-only twins
@@ -18,6 +19,9 @@
 //   crh_reproject.cpp  reprojected display history: the image an ending view displayed, blended into the next view's in front of the denoise filter
 //                      (reproject_kernels.hip), the capture in crh_set_camera, the host-only twin
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
+//
+// Shared by those, below: display_source (the image a read-out shows), grow_display_scratch, geometry_changed / geom_gen and side_upload (the tables derived from the
+// geometry), DerivedStamp (what the outline mask and the denoise guide were computed from), camera_frame (the ONE copy of the camera basis), time_launches, aligned_copy
 //
 // This is the code that sits behind CADRays' `myInternal->View->Redraw()` (reference src/Launcher/AppViewer.cxx:1047).  There is NO CPU fallback:
 // every entry point that renders or traces launches the gfx950 kernels and reports CRH_E_DEVICE when the HIP runtime refuses.
@@ -31,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -236,6 +241,13 @@ struct ReadbackState {
   bool meter_on = false; crh_meter_params meter_par{}; DevBuf<DMeter> d_meter;
 };
 
+// ---- what a buffer DERIVED from the id buffer and the per-triangle table (the outline mask, the denoise guide) was computed from: it is stale when the stamp of the
+// state in force differs.  ids_gen and table_gen of a computed buffer are never 0, so a default stamp means "none".
+struct DerivedStamp {
+  uint64_t ids_gen = 0, table_gen = 0; uint32_t w = 0, h = 0, par[2] = {0u, 0u};
+  bool operator==(const DerivedStamp& o) const { return ids_gen == o.ids_gen && table_gen == o.table_gen && w == o.w && h == o.h && par[0] == o.par[0] && par[1] == o.par[1]; }
+};
+
 // ---- the first-hit id buffer (crh_pick.cpp): DERIVED state -- object / triangle / distance under every pixel centre for the camera, target size, geometry, transforms,
 // visibility flags and tree in force.  do_reset and crh_set_camera clear ids_valid; the buffer is computed on the first pick / id read-back / overlaid LDR read-out after
 // that, on a stream of its own (crh_render never launches it), kept on the device, and a further crh_pick is one 16-byte copy.  Selection and hover are plain host
@@ -244,7 +256,7 @@ struct PickState {
   hipStream_t pk_stream = nullptr; hipEvent_t pk_fork = nullptr;
   DevBuf<float4> d_pk_rays, d_pk_hit_slot;                                                   // per ray slot (8x8-block order): the ray, what the traversal kernel answered
   DevBuf<float4> d_pk_hit; DevBuf<int32_t> d_pk_obj;                                         // per pixel, row-major: {t, u, v, caller's triangle index}, object
-  DevBuf<int32_t> d_pk_tri_obj; bool pk_tri_obj_dirty = true;                                // c->tri_obj on the device (uploaded on first need after crh_build / crh_add_object)
+  DevBuf<int32_t> d_pk_tri_obj; uint64_t pk_tri_obj_gen = 0;                                 // c->tri_obj on the device, and the geom_gen it was uploaded at (on first need after a change)
   DevBuf<uint32_t> d_pk_cursor; DevBuf<DCounters> d_pk_counters;                             // work cursor and counter block of the id pass (crh_stats never sees its rays)
   bool ids_valid = false; uint32_t ids_w = 0, ids_h = 0;
   uint64_t ids_gen = 0;                                                                      // bumped whenever ensure_ids recomputes: what is derived from the buffer (the outline mask) knows when it is stale
@@ -256,7 +268,7 @@ struct PickState {
 // ---- view fitting (crh_fit.cpp): one float4 {x, y, z, object} per vertex on the device, built from pos / tri / tri_obj and uploaded by the FIRST crh_fit_view after
 // the geometry changed (a host that never fits pays no memory and no time); the per-call object table and the records the kernel fills
 struct FitState {
-  DevBuf<float4> d_fit_verts; uint32_t fit_n = 0; bool fit_verts_dirty = true;
+  DevBuf<float4> d_fit_verts; uint32_t fit_n = 0; uint64_t fit_verts_gen = 0;      // (the geom_gen the array was built from)
   DevBuf<void> d_fit_objs; DevBuf<uint32_t> d_fit_rec;      // room for the same number of objects in both
 };
 
@@ -270,9 +282,8 @@ struct RegionState {
 // id buffer and the table and kept while neither, nor the frame size, nor the two thresholds change.  A host that never switches the feature on pays nothing.
 struct OutlineState {
   bool ol_on = false; crh_outline_params ol_par{};
-  DevBuf<void> d_ol_table; uint32_t ol_n_tri = 0; bool ol_table_dirty = true; uint64_t ol_table_gen = 0;
-  DevBuf<uint8_t> d_ol_mask; bool ol_mask_valid = false;
-  uint64_t ol_mask_ids_gen = 0, ol_mask_table_gen = 0; uint32_t ol_mask_w = 0, ol_mask_h = 0; float ol_mask_crease = 0.f, ol_mask_ratio = 0.f;      // what the mask was computed from
+  DevBuf<void> d_ol_table; uint32_t ol_n_tri = 0; uint64_t ol_table_gen = 0;      // (the geom_gen the table was built from)
+  DevBuf<uint8_t> d_ol_mask; DerivedStamp ol_mask_stamp;                          // what the mask was computed from: par = the bits of crease_cos, depth_ratio
 };
 
 // ---- denoised display (crh_denoise.cpp): display state like the feature lines -- only the tone map of an LDR read-out (and crh_read_denoised) looks at it.  The guide
@@ -281,8 +292,7 @@ struct OutlineState {
 // in stream order and so share it.  A host that never switches the feature on pays nothing.
 struct DenoiseState {
   bool dn_on = false; crh_denoise_params dn_par{};
-  DevBuf<float4> d_dn_guide; DevBuf<int2> d_dn_ids; bool dn_guide_valid = false;
-  uint64_t dn_guide_ids_gen = 0, dn_guide_table_gen = 0; uint32_t dn_guide_w = 0, dn_guide_h = 0;      // what the guide was computed from
+  DevBuf<float4> d_dn_guide; DevBuf<int2> d_dn_ids; DerivedStamp dn_guide_stamp;      // what the guide was computed from (par stays 0)
   DevBuf<float4> d_dn_img[2][2];
   bool dn_staged = true;            // steps 1 and 2 take the LDS-staged kernel (denoise_kernels.hip): 67 - 72 against 77 - 85 us per pass at 1080p; CRH_DENOISE_STAGED=0: the plain gather; the same bytes either way
 };
@@ -314,6 +324,7 @@ struct TimingState {
 
 struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ReprojectState, crh::TimingState {
   int device = 0;
+  uint64_t geom_gen = 1;  // THE GEOMETRY GENERATION: geometry_changed() bumps it; every table derived from pos / tri / tri_obj remembers the one it was built from (0: none yet)
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
   int cus = 0;            // compute units (0: unknown)
   int grid = 1024;        // streaming / shading kernels: 4 workgroups per CU = what k_shade's 128 VGPRs keep resident; every workgroup of the
@@ -387,6 +398,78 @@ inline int grow_u32(crh_ctx* c, DevBuf<uint32_t>& d, size_t n)
   return CRH_OK;
 }
 
+// The image a read-out shows: the frame crh_reduce assembled while it is valid, else this context's own accumulator
+inline const float4* display_source(const crh_ctx* c) { return c->assembled_valid ? c->d_assembled : c->d_accum; }
+
+// Room for n pixels in each of the `count` display scratch images at d, which belong to scratch set `set`.  Set 0 is read and written on the context's stream by calls
+// that end with a wait for it: nothing is in flight.  Set 1 belongs to the read-back stream, which is waited for before a block goes.
+inline int grow_display_scratch(crh_ctx* c, int set, DevBuf<float4>* d, int count, size_t n)
+{
+  bool room = true;
+  for (int k = 0; k < count; ++k) room = room && d[k].cap() >= n;
+  if (room) return CRH_OK;
+  if (set == 1) CRH_HIP(hipStreamSynchronize(c->rb_stream));
+  for (int k = 0; k < count; ++k) CRH_HIP(d[k].reserve(n));
+  return CRH_OK;
+}
+
+// pos / tri / tri_obj changed (crh_set_geometry, crh_add_object, crh_build -- nowhere else): every table derived from them is stale
+inline void geometry_changed(crh_ctx* c) { ++c->geom_gen; }
+
+// n records from the host into a derived device table on the side stream (pick_stream first): grown with a quarter of head-room (crh_add_object grows the scene a
+// little at a time) and waited for, so `src` may be a temporary
+template <class Rec, class T> int side_upload(crh_ctx* c, DevBuf<T>& d, const Rec* src, size_t n)
+{
+  constexpr size_t per = sizeof(Rec) / DevBuf<T>::elem;
+  CRH_HIP(d.reserve(per * n, per * (n / 4)));
+  if (n) CRH_HIP(hipMemcpyAsync(d, src, sizeof(Rec) * n, hipMemcpyHostToDevice, c->pk_stream));
+  CRH_HIP(hipStreamSynchronize(c->pk_stream));
+  return CRH_OK;
+}
+
+// Time `repeats` calls of launch() -- it enqueues on `on` and returns the HIP status -- between two events: their mean in *mean_ms.  Whatever went wrong, `on` has been
+// waited for when this returns: the events, and the call-local buffers the launches used, may go.
+template <class F> hipError_t time_launches(hipStream_t on, uint32_t repeats, F&& launch, float* mean_ms)
+{
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.f;
+  hipError_t e = hipEventCreate(&e0);
+  if (e == hipSuccess) e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = hipEventRecord(e0, on);
+  for (uint32_t r = 0; r < repeats && e == hipSuccess; ++r) e = launch();
+  if (e == hipSuccess) e = hipEventRecord(e1, on);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  const hipError_t e2 = hipStreamSynchronize(on);
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  if (mean_ms) *mean_ms = ms / (float)repeats;
+  return e != hipSuccess ? e : e2;
+}
+
+// The host twins: n elements of aligned storage in v, filled from the caller's bytes at src, which need not be aligned (nullptr: left zeroed)
+template <class T> int aligned_copy(std::vector<T>& v, const void* src, size_t n)
+{
+  try { v.resize(n); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
+  if (src && n) std::memcpy(v.data(), src, sizeof(T) * n);
+  return CRH_OK;
+}
+
+// THE CAMERA FRAME of `cam` over a W x H target: the one copy of these expressions -- the kernels' DScene (fill_scene), the view fit (crh_fit.cpp) and the frame a
+// reprojection history keeps (crh_reproject.cpp) must agree to the bit (tests/test_display_chain.py)
+struct CameraFrame { crh_v3 fwd, right, up; float tan_half, aspect; };
+inline CameraFrame camera_frame(const crh_camera& cam, uint32_t W, uint32_t H)
+{
+  CameraFrame f;
+  f.fwd = crh_norm3(crh_mk3(cam.dir[0], cam.dir[1], cam.dir[2]));
+  f.right = crh_norm3(crh_cross3(f.fwd, crh_mk3(cam.up[0], cam.up[1], cam.up[2])));
+  f.up = crh_cross3(f.right, f.fwd);
+  float s, cs; crh_sincos((cam.fovy_deg * 0.5f) * (CRH_PI / 180.0f), &s, &cs);
+  f.tan_half = s / cs;
+  f.aspect = cam.aspect > 0.f ? cam.aspect : (float)W / (float)H;
+  return f;
+}
+
 // ---- crh_scene.cpp
 void fill_scene(const crh_ctx* c, DScene& S);
 int upload_textures(crh_ctx* c);
@@ -401,7 +484,7 @@ int fork_from_context(crh_ctx* c);              // ... made to start behind what
 int wait_overlay_readers(crh_ctx* c);
 // ---- crh_outline.cpp
 int outline_ldr(crh_ctx* c, hipStream_t on, uint8_t* d_ldr);      // feature lines over the tone-mapped bytes at d_ldr, enqueued on `on`, BEFORE overlay_ldr; nothing at all while the feature is off
-int ensure_outline_table(crh_ctx* c);                              // the per-triangle table of the geometry in force, built and uploaded on first need (after ensure_ids)
+int ensure_ids_and_table(crh_ctx* c);                              // what the outline mask and the denoise guide are derived from, valid on return: ensure_ids, the device set, the side stream, the per-triangle table of the geometry in force
 // ---- crh_denoise.cpp
 // The image the tone map of an LDR read-out reads, in *shown: `src` itself while the feature is off or there is no scene (nothing is allocated, nothing is launched),
 // else the filtered image of scratch set `set` (0: the context's stream, 1: the read-back stream), its passes enqueued on `on`.  Called just BEFORE launch_tonemap,

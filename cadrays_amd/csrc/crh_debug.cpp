@@ -40,16 +40,9 @@ int crh_bench_trace(crh_ctx* c, const float* rays, uint32_t n, int any_hit, uint
   CRH_HIP(hipMemcpyAsync(base, rays, in_b, hipMemcpyHostToDevice, cstream(c)));
   DScene S; fill_scene(c, S);
   Launch L{cstream(c), c->grid_trace, false, c->clamp_grid ? c->cus : 0};
-  launch_trace_rays(L, S, (const float4*)base, n, any_hit, (float4*)(base + in_b), (uint32_t*)(base + in_b), c->d_api_cursor, c->d_counters);
-  hipEvent_t e0 = get_event(c), e1 = get_event(c);
-  CRH_HIP(hipEventRecord(e0, cstream(c)));
-  for (uint32_t r = 0; r < repeat; ++r)
-    launch_trace_rays(L, S, (const float4*)base, n, any_hit, (float4*)(base + in_b), (uint32_t*)(base + in_b), c->d_api_cursor, c->d_counters);
-  CRH_HIP(hipEventRecord(e1, cstream(c)));
-  CRH_HIP(hipStreamSynchronize(cstream(c)));
-  float ms = 0.f; CRH_HIP(hipEventElapsedTime(&ms, e0, e1));
-  c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
-  *avg_ms = ms / (float)repeat;
+  auto launch = [&] { launch_trace_rays(L, S, (const float4*)base, n, any_hit, (float4*)(base + in_b), (uint32_t*)(base + in_b), c->d_api_cursor, c->d_counters); return hipGetLastError(); };
+  CRH_HIP(launch());                                     // the code is loaded
+  CRH_HIP(time_launches(L.stream, repeat, launch, avg_ms));
   return CRH_OK;
 }
 

@@ -5,8 +5,6 @@
 // pass per level.  The rules have ONE copy (denoise_kernels.h), compiled for the kernels and for the host twin below.  Display state: nothing of the rendering
 // state is touched, and only the tone map's source changes.  DESIGN.md section 4.12.
 // (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
-#include <new>
-
 #include "crh_context.h"
 #include "denoise_kernels.h"
 
@@ -29,6 +27,13 @@ const char* params_refused(const crh_denoise_params* p)
   return nullptr;
 }
 
+crh_denoise_params params_in_force(const crh_ctx* c)
+{
+  crh_denoise_params p; crh_denoise_defaults(&p);
+  if (c->dn_on) p = c->dn_par;
+  return p;
+}
+
 DenoiseRule rule_of(const crh_denoise_params& p) { return DenoiseRule{p.levels, p.normal_cos, p.depth_ratio, (float)p.until_samples}; }      // (2^20 is exact)
 
 // The passes of rule R from `src` through the two images of scratch set `set`, enqueued on `on`; *shown = the image the last pass wrote.
@@ -38,11 +43,7 @@ int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const Denoise
   const uint32_t W = c->par.width, H = c->par.height;
   const size_t n = (size_t)W * H;
   DevBuf<float4>* img = c->d_dn_img[set];
-  if (img[0].cap() < n || img[1].cap() < n) {
-    // Set 0 is read and written on the context's stream by calls that end with a wait for it: nothing is in flight.  Set 1 belongs to the read-back stream.
-    if (set == 1) CRH_HIP(hipStreamSynchronize(c->rb_stream));
-    CRH_HIP(img[0].reserve(n)); CRH_HIP(img[1].reserve(n));
-  }
+  if (int rc = grow_display_scratch(c, set, img, 2, n)) return rc;
   const float4* in = src;
   for (uint32_t k = 0; k < R.levels; ++k) {
     float4* out = img[k & 1u];
@@ -62,19 +63,17 @@ namespace api {
 // The guide of the state in force, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids and the outline mask are).
 int ensure_guide(crh_ctx* c)
 {
-  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
-  CRH_HIP(hipSetDevice(c->device));
-  if ((rc = pick_stream(c))) return rc;
-  if ((rc = ensure_outline_table(c))) return rc;
+  int rc = ensure_ids_and_table(c); if (rc) return rc;
   const uint32_t W = c->par.width, H = c->par.height;
-  if (c->dn_guide_valid && c->dn_guide_ids_gen == c->ids_gen && c->dn_guide_table_gen == c->ol_table_gen && c->dn_guide_w == W && c->dn_guide_h == H) return CRH_OK;
+  const DerivedStamp now{c->ids_gen, c->ol_table_gen, W, H, {0u, 0u}};
+  if (c->dn_guide_stamp == now) return CRH_OK;
   if ((rc = wait_overlay_readers(c))) return rc;         // an asynchronous read-back may still be filtering from the guide
-  c->dn_guide_valid = false;
+  c->dn_guide_stamp = DerivedStamp{};
   CRH_HIP(c->d_dn_guide.reserve((size_t)W * H)); CRH_HIP(c->d_dn_ids.reserve((size_t)W * H));      // (what read the old blocks has been waited for: the synchronous
   launch_denoise_guide(c->pk_stream, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids);      //  read-outs end with a wait, the readers just above)
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipStreamSynchronize(c->pk_stream));
-  c->dn_guide_valid = true; c->dn_guide_ids_gen = c->ids_gen; c->dn_guide_table_gen = c->ol_table_gen; c->dn_guide_w = W; c->dn_guide_h = H;
+  c->dn_guide_stamp = now;
   return CRH_OK;
 }
 
@@ -115,7 +114,7 @@ int crh_set_denoise(crh_ctx* c, const crh_denoise_params* p)
 int crh_get_denoise(crh_ctx* c, crh_denoise_params* out, int* on)
 {
   if (!c) return CRH_E_INVALID;
-  if (out) { if (c->dn_on) *out = c->dn_par; else crh_denoise_defaults(out); }
+  if (out) *out = params_in_force(c);
   if (on) *on = c->dn_on ? 1 : 0;
   return CRH_OK;
 }
@@ -126,13 +125,11 @@ int crh_read_denoised(crh_ctx* c, float* rgba_out)
   if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
   if (!c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
   c->read_since_render = true;
-  crh_denoise_params p; crh_denoise_defaults(&p);
-  if (c->dn_on) p = c->dn_par;
   CRH_HIP(hipSetDevice(c->device));
   const float4* shown = nullptr;
   hipStream_t on = cstream(c);
-  if (int rc = reproject_src(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, &shown)) return rc;      // what a read-out's filter receives (crh_reproject.cpp): the accumulator itself while that feature is off
-  if (int rc = filter(c, on, shown, 0, rule_of(p), &shown)) return rc;
+  if (int rc = reproject_src(c, on, display_source(c), 0, &shown)) return rc;      // what a read-out's filter receives (crh_reproject.cpp): the accumulator itself while that feature is off
+  if (int rc = filter(c, on, shown, 0, rule_of(params_in_force(c)), &shown)) return rc;
   CRH_HIP(hipMemcpyAsync(rgba_out, shown, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, on));
   CRH_HIP(hipStreamSynchronize(on));
   return CRH_OK;
@@ -143,39 +140,22 @@ int crh_bench_denoise(crh_ctx* c, uint32_t repeats, float* guide_ms, float* pass
   if (!c || !repeats || !pass_ms) return fail(c, CRH_E_INVALID, "crh_bench_denoise: null output / no repeats");
   if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
   if (!c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
-  crh_denoise_params p; crh_denoise_defaults(&p);
-  if (c->dn_on) p = c->dn_par;
-  const DenoiseRule R = rule_of(p);
+  const DenoiseRule R = rule_of(params_in_force(c));
   CRH_HIP(hipSetDevice(c->device));
   hipStream_t on = cstream(c);
   const float4* shown = nullptr;
-  if (int rc = filter(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, R, &shown)) return rc;      // guide and images exist, the code is loaded
+  if (int rc = filter(c, on, display_source(c), 0, R, &shown)) return rc;      // guide and images exist, the code is loaded
   if (int rc = wait_overlay_readers(c)) return rc;                                                            // the guide is rewritten below, with what it holds
   CRH_HIP(hipStreamSynchronize(on));
   const uint32_t W = c->par.width, H = c->par.height;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  CRH_HIP(hipEventCreate(&e0));
-  hipError_t e = hipEventCreate(&e1);
-  float ms = 0.f;
-  auto timed = [&](auto&& launch, float* out) {
-    if (e == hipSuccess) e = hipEventRecord(e0, on);
-    for (uint32_t r = 0; r < repeats && e == hipSuccess; ++r) { launch(); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipEventRecord(e1, on);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (out) *out = ms / (float)repeats;
-  };
-  timed([&] { launch_denoise_guide(on, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids); }, guide_ms);
-  const float4* in = c->assembled_valid ? c->d_assembled : c->d_accum;
   for (uint32_t k = 0; k < kDenoiseMaxLevels; ++k) pass_ms[k] = 0.f;
+  CRH_HIP(time_launches(on, repeats, [&] { launch_denoise_guide(on, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, c->d_dn_guide, c->d_dn_ids); return hipGetLastError(); }, guide_ms));
+  const float4* in = display_source(c);
   for (uint32_t k = 0; k < R.levels; ++k) {          // pass k from the image pass k - 1 left, over and over: the same bytes every time
     float4* out = c->d_dn_img[0][k & 1u];
-    timed([&] { launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged); }, &pass_ms[k]);
+    CRH_HIP(time_launches(on, repeats, [&] { launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged); return hipGetLastError(); }, &pass_ms[k]));
     in = out;
   }
-  const hipError_t e2 = hipStreamSynchronize(on);     // whatever went wrong: nothing still uses the two events when they go
-  hipEventDestroy(e0); if (e1) hipEventDestroy(e1);
-  CRH_HIP(e); CRH_HIP(e2);
   return CRH_OK;
 }
 
@@ -186,9 +166,7 @@ int crh_denoise_host(const float* rgba, const int32_t* object_px, const int32_t*
   if (params_refused(p)) return CRH_E_INVALID;
   const size_t n = (size_t)width * height;
   std::vector<OutlineTri> tb; std::vector<float4> in, tmp, out;      // (the caller's bytes need not be aligned)
-  try { tb.resize(n_tri); in.resize(n); tmp.resize(n); out.resize(n); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
-  if (n_tri) std::memcpy(tb.data(), table, sizeof(OutlineTri) * (size_t)n_tri);
-  std::memcpy(in.data(), rgba, sizeof(float4) * n);
+  if (aligned_copy(tb, table, n_tri) || aligned_copy(in, rgba, n) || aligned_copy(tmp, nullptr, n) || aligned_copy(out, nullptr, n)) return CRH_E_NOMEM;
   denoise_host(object_px, triangle_px, t_px, width, height, tb.data(), n_tri, rule_of(*p), in.data(), tmp.data(), out.data());
   std::memcpy(rgba_out, out.data(), sizeof(float4) * n);
   return CRH_OK;

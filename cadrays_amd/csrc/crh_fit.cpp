@@ -22,18 +22,15 @@ bool finite_camera(const crh_camera& cam)
   return all_finite(v, sizeof v / sizeof v[0]);
 }
 
-// The frame and the slopes.  right / up / fwd, tan_half and aspect exactly as fill_scene derives them (crh_scene.cpp); kx and ky in double, rounded once.
+// The frame and the slopes.  right / up / fwd, tan_half and aspect are camera_frame's (crh_context.h), as fill_scene's are; kx and ky in double, rounded once.
 const char* fit_setup(const crh_camera& cam, uint32_t W, uint32_t H, float margin, FitSetup& S)
 {
   if (!(margin >= 0.f && margin <= 0.9f)) return "margin outside [0, 0.9]";
   if (!finite_camera(cam)) return "the camera holds a NaN / Inf";
   if (!(cam.aspect > 0.f) && (!W || !H)) return "aspect <= 0 needs a target size";
-  const crh_v3 fwd = crh_norm3(crh_mk3(cam.dir[0], cam.dir[1], cam.dir[2]));
-  const crh_v3 right = crh_norm3(crh_cross3(fwd, crh_mk3(cam.up[0], cam.up[1], cam.up[2])));
-  const crh_v3 up = crh_cross3(right, fwd);
-  float s, cs; crh_sincos((cam.fovy_deg * 0.5f) * (CRH_PI / 180.0f), &s, &cs);
-  S.tan_half = s / cs;
-  S.aspect = cam.aspect > 0.f ? cam.aspect : (float)W / (float)H;
+  const CameraFrame cf = camera_frame(cam, W, H);
+  const crh_v3 fwd = cf.fwd, right = cf.right, up = cf.up;
+  S.tan_half = cf.tan_half; S.aspect = cf.aspect;
   FitFrame& F = S.F;
   for (int a = 0; a < 3; ++a) F.pivot[a] = cam.eye[a];
   F.right[0] = right.x; F.right[1] = right.y; F.right[2] = right.z;
@@ -150,13 +147,10 @@ int crh_fit_view(crh_ctx* c, const crh_camera* cam_in, const uint8_t* chosen, ui
   }
   CRH_HIP(hipSetDevice(c->device));
   int rc = pick_stream(c); if (rc) return rc;
-  if (c->fit_verts_dirty) {                              // the first fit after the geometry changed: build the array and upload it
+  if (c->fit_verts_gen != c->geom_gen) {                 // the first fit after the geometry changed: build the array and upload it
     std::vector<float> v4; build_fit_verts(c, v4);
-    const size_t nV = v4.size() / 4;
-    CRH_HIP(c->d_fit_verts.reserve(nV, nV / 4));        // crh_add_object grows it a little at a time
-    if (nV) CRH_HIP(hipMemcpyAsync(c->d_fit_verts, v4.data(), sizeof(float4) * nV, hipMemcpyHostToDevice, c->pk_stream));
-    CRH_HIP(hipStreamSynchronize(c->pk_stream));         // v4 is a temporary
-    c->fit_n = (uint32_t)nV; c->fit_verts_dirty = false;
+    if ((rc = side_upload(c, c->d_fit_verts, reinterpret_cast<const float4*>(v4.data()), v4.size() / 4))) return rc;
+    c->fit_n = (uint32_t)(v4.size() / 4); c->fit_verts_gen = c->geom_gen;
   }
   CRH_HIP(c->d_fit_objs.reserve(sizeof(FitObject) * nO, sizeof(FitObject) * 16)); CRH_HIP(c->d_fit_rec.reserve((size_t)kFitRec * nO, (size_t)kFitRec * 16));
   std::vector<uint32_t> rec((size_t)kFitRec * nO, 0u);

@@ -4,8 +4,6 @@
 // per pixel, derived from the id buffer and a per-triangle table, kept until one of them changes -- and the drawing.  The rules have ONE copy (outline_kernels.h),
 // compiled for the kernels and for the host twins below.  Display state: nothing of the rendering state is touched.  DESIGN.md section 4.11.
 // (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
-#include <new>
-
 #include "crh_context.h"
 #include "outline_kernels.h"
 
@@ -34,6 +32,13 @@ const char* params_refused(const crh_outline_params* p)
   return thresholds_refused(p->crease_cos, p->depth_ratio);
 }
 
+crh_outline_params params_in_force(const crh_ctx* c)
+{
+  crh_outline_params p; crh_outline_defaults(&p);
+  if (c->ol_on) p = c->ol_par;
+  return p;
+}
+
 OutlineDraw draw_of(const crh_outline_params& p) { return OutlineDraw{p.kinds, p.width, p.rgb[0], p.rgb[1], p.rgb[2], p.alpha}; }
 
 // the records of n_tri triangles (rows of 4 words: v0, v1, v2, material); false: an index beyond the vertices
@@ -47,29 +52,33 @@ bool build_table(const float* pos, size_t n_vertices, const uint32_t* tri, size_
   return true;
 }
 
+// The per-triangle table of the geometry in force, on the device, valid when this returns (the side stream exists).  Shared with the denoised display
+// (crh_denoise.cpp), which reads the normals.
+int ensure_outline_table(crh_ctx* c)
+{
+  if (c->ol_table_gen == c->geom_gen) return CRH_OK;
+  const size_t nT = c->tri.size() / 4;                   // the first need after the geometry changed: build the table and upload it
+  std::vector<OutlineTri> table;
+  if (aligned_copy(table, nullptr, nT)) return fail(c, CRH_E_NOMEM, "no memory for the outline table");
+  if (!build_table(c->pos.data(), c->pos.size() / 3, reinterpret_cast<const uint32_t*>(c->tri.data()), nT, table.data()))
+    return fail(c, CRH_E_INVALID, "a triangle refers to a vertex that does not exist");
+  if (int rc = wait_overlay_readers(c)) return rc;       // a read-back in flight draws from a mask, not from the table; the mask kernel itself ran synchronously
+  if (int rc = side_upload(c, c->d_ol_table, table.data(), nT)) return rc;
+  c->ol_n_tri = (uint32_t)nT; c->ol_table_gen = c->geom_gen;
+  return CRH_OK;
+}
+
 }  // namespace
 
 namespace crh {
 namespace api {
 
-// The per-triangle table of the geometry in force, on the device, valid when this returns (the side stream exists: ensure_ids comes first).  Shared with the
-// denoised display (crh_denoise.cpp), which reads the normals.
-int ensure_outline_table(crh_ctx* c)
+int ensure_ids_and_table(crh_ctx* c)
 {
-  int rc;
-  if (c->ol_table_dirty) {                               // the first need after the geometry changed: build the table and upload it
-    const size_t nT = c->tri.size() / 4;
-    std::vector<OutlineTri> table;
-    try { table.resize(nT); } catch (const std::bad_alloc&) { return fail(c, CRH_E_NOMEM, "no memory for the outline table"); }
-    if (!build_table(c->pos.data(), c->pos.size() / 3, reinterpret_cast<const uint32_t*>(c->tri.data()), nT, table.data()))
-      return fail(c, CRH_E_INVALID, "a triangle refers to a vertex that does not exist");
-    if ((rc = wait_overlay_readers(c))) return rc;       // a read-back in flight draws from a mask, not from the table; the mask kernel itself ran synchronously
-    CRH_HIP(c->d_ol_table.reserve(sizeof(OutlineTri) * nT, sizeof(OutlineTri) * (nT / 4)));      // crh_add_object grows it a little at a time
-    if (nT) CRH_HIP(hipMemcpyAsync(c->d_ol_table, table.data(), sizeof(OutlineTri) * nT, hipMemcpyHostToDevice, c->pk_stream));
-    CRH_HIP(hipStreamSynchronize(c->pk_stream));         // `table` is a temporary
-    c->ol_n_tri = (uint32_t)nT; c->ol_table_dirty = false; ++c->ol_table_gen;
-  }
-  return CRH_OK;
+  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
+  CRH_HIP(hipSetDevice(c->device));
+  if ((rc = pick_stream(c))) return rc;
+  return ensure_outline_table(c);
 }
 
 }  // namespace api
@@ -80,22 +89,17 @@ namespace {
 // The mask of the state in force for these thresholds, on the device, valid when this returns (computed on the side stream and waited for, as ensure_ids does).
 int ensure_mask(crh_ctx* c, float crease_cos, float depth_ratio)
 {
-  int rc = ensure_ids(c); if (rc) return rc;             // (checks c->built, sets the device, creates the side stream)
-  CRH_HIP(hipSetDevice(c->device));
-  if ((rc = pick_stream(c))) return rc;
+  int rc = ensure_ids_and_table(c); if (rc) return rc;
   const uint32_t W = c->par.width, H = c->par.height;
-  if ((rc = ensure_outline_table(c))) return rc;
-  if (c->ol_mask_valid && c->ol_mask_ids_gen == c->ids_gen && c->ol_mask_table_gen == c->ol_table_gen && c->ol_mask_w == W && c->ol_mask_h == H &&
-      crh_f2u(c->ol_mask_crease) == crh_f2u(crease_cos) && crh_f2u(c->ol_mask_ratio) == crh_f2u(depth_ratio))
-    return CRH_OK;
+  const DerivedStamp now{c->ids_gen, c->ol_table_gen, W, H, {crh_f2u(crease_cos), crh_f2u(depth_ratio)}};
+  if (c->ol_mask_stamp == now) return CRH_OK;
   if ((rc = wait_overlay_readers(c))) return rc;         // an asynchronous read-back may still be drawing from the mask
-  c->ol_mask_valid = false;
+  c->ol_mask_stamp = DerivedStamp{};
   CRH_HIP(c->d_ol_mask.reserve((size_t)W * H));          // (what read the old block has been waited for: this stream runs synchronously, the readers just above)
   launch_outline_mask(c->pk_stream, c->d_pk_obj, c->d_pk_hit, W, H, c->d_ol_table.as<const OutlineTri>(), c->ol_n_tri, crease_cos, depth_ratio, c->d_ol_mask);
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipStreamSynchronize(c->pk_stream));
-  c->ol_mask_valid = true; c->ol_mask_ids_gen = c->ids_gen; c->ol_mask_table_gen = c->ol_table_gen; c->ol_mask_w = W; c->ol_mask_h = H;
-  c->ol_mask_crease = crease_cos; c->ol_mask_ratio = depth_ratio;
+  c->ol_mask_stamp = now;
   return CRH_OK;
 }
 
@@ -143,7 +147,7 @@ int crh_set_outline(crh_ctx* c, const crh_outline_params* p)
 int crh_get_outline(crh_ctx* c, crh_outline_params* out, int* on)
 {
   if (!c) return CRH_E_INVALID;
-  if (out) { if (c->ol_on) *out = c->ol_par; else crh_outline_defaults(out); }
+  if (out) *out = params_in_force(c);
   if (on) *on = c->ol_on ? 1 : 0;
   return CRH_OK;
 }
@@ -152,8 +156,7 @@ int crh_read_outline(crh_ctx* c, uint8_t* mask_out)
 {
   if (!c || !mask_out) return fail(c, CRH_E_INVALID, "crh_read_outline: null output");
   if (!c->built) return fail(c, CRH_E_NOTBUILT, "crh_build has not been called");
-  crh_outline_params p; crh_outline_defaults(&p);
-  if (c->ol_on) p = c->ol_par;
+  const crh_outline_params p = params_in_force(c);
   if (int rc = ensure_mask(c, p.crease_cos, p.depth_ratio)) return rc;
   CRH_HIP(hipMemcpyAsync(mask_out, c->d_ol_mask, (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, c->pk_stream));
   CRH_HIP(hipStreamSynchronize(c->pk_stream));
@@ -164,7 +167,7 @@ int crh_outline_table_host(const float* pos, uint32_t n_vertices, const uint32_t
 {
   if (!pos || !tri || !table_out || !n_vertices || !n_tri) return CRH_E_INVALID;
   std::vector<OutlineTri> table;      // (table_out need not be aligned)
-  try { table.resize(n_tri); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
+  if (aligned_copy(table, nullptr, n_tri)) return CRH_E_NOMEM;
   if (!build_table(pos, n_vertices, tri, n_tri, table.data())) return CRH_E_INVALID;
   std::memcpy(table_out, table.data(), sizeof(OutlineTri) * (size_t)n_tri);
   return CRH_OK;
@@ -176,8 +179,7 @@ int crh_outline_mask_host(const int32_t* object_px, const int32_t* triangle_px, 
   if (!object_px || !triangle_px || !t_px || !mask_out || !width || !height || (n_tri && !table)) return CRH_E_INVALID;
   if (thresholds_refused(crease_cos, depth_ratio)) return CRH_E_INVALID;
   std::vector<OutlineTri> tb;         // (the caller's bytes need not be aligned)
-  try { tb.resize(n_tri); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
-  if (n_tri) std::memcpy(tb.data(), table, sizeof(OutlineTri) * (size_t)n_tri);
+  if (aligned_copy(tb, table, n_tri)) return CRH_E_NOMEM;
   outline_mask_host(object_px, triangle_px, t_px, width, height, tb.data(), n_tri, crease_cos, depth_ratio, mask_out);
   return CRH_OK;
 }

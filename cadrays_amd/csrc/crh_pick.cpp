@@ -29,11 +29,8 @@ int ensure_ids(crh_ctx* c)
   const size_t n_slots = 64 * (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u), n_px = (size_t)W * H;
   CRH_HIP(c->d_pk_rays.reserve(2 * n_slots)); CRH_HIP(c->d_pk_hit_slot.reserve(n_slots));      // (what read the old blocks has been waited for: this stream runs
   CRH_HIP(c->d_pk_hit.reserve(n_px)); CRH_HIP(c->d_pk_obj.reserve(n_px));                       //  synchronously, the overlay's readers just above)
-  if (c->pk_tri_obj_dirty && !c->tri_obj.empty()) {
-    CRH_HIP(c->d_pk_tri_obj.reserve(c->tri_obj.size(), c->tri_obj.size() / 4));      // crh_add_object grows it a little at a time
-    CRH_HIP(hipMemcpyAsync(c->d_pk_tri_obj, c->tri_obj.data(), sizeof(int32_t) * c->tri_obj.size(), hipMemcpyHostToDevice, c->pk_stream));
-  }
-  c->pk_tri_obj_dirty = false;
+  if (c->pk_tri_obj_gen != c->geom_gen && !c->tri_obj.empty() && (rc = side_upload(c, c->d_pk_tri_obj, c->tri_obj.data(), c->tri_obj.size()))) return rc;
+  c->pk_tri_obj_gen = c->geom_gen;                       // (also of a scene without objects: there is nothing to upload)
   if ((rc = fork_from_context(c))) return rc;
   DScene S; fill_scene(c, S);
   Launch Ls{c->pk_stream, c->grid, false};

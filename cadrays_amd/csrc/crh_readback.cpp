@@ -39,6 +39,24 @@ static int ensure_meter_blocks(crh_ctx* c)
   return CRH_OK;
 }
 
+// THE DISPLAY CHAIN: everything between the image a read-out shows and the RGB8 bytes at d_ldr, enqueued on L.stream -- the one place where a
+// display feature is inserted.  `set`: the scratch images of the denoise filter and the reprojection (0: the context's stream, 1: the read-back stream); `block`: the
+// metering block.  The caller owns the stream: nothing here calls cstream().
+static int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block, uint8_t* d_ldr)
+{
+  const uint32_t n = c->par.width * c->par.height;
+  const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
+  const bool tiles = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;      // ShowSamplingTiles: d_picked was written by the device-side tile draw of the last iteration
+  const float4* src = display_source(c);
+  const float* metered = meter_in_front(c, L, src, block);                // auto exposure meters the UNFILTERED image ...
+  const float4* shown;
+  if (int rc = reproject_src(c, L.stream, src, set, &shown)) return rc;   // ... reprojected display history (crh_reproject.cpp) and ...
+  if (int rc = denoise_src(c, L.stream, shown, set, &shown)) return rc;   // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
+  launch_tonemap(L, shown, d_ldr, n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, tiles ? c->d_picked : nullptr, c->par.width, ts, metered);
+  if (int rc = outline_ldr(c, L.stream, d_ldr)) return rc;                // feature lines (crh_outline.cpp): nothing at all while the feature is off
+  return overlay_ldr(c, L.stream, d_ldr);                                 // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
+}
+
 extern "C" {
 
 int crh_read_hdr(crh_ctx* c, float* out)
@@ -49,7 +67,7 @@ int crh_read_hdr(crh_ctx* c, float* out)
   const uint32_t n = c->par.width * c->par.height;
   CRH_HIP(c->d_scratch.reserve(sizeof(float) * 3 * (size_t)n));
   Launch L{cstream(c), c->grid, false};
-  launch_hdr(L, c->assembled_valid ? c->d_assembled : c->d_accum, c->d_scratch.as<float>(), n);
+  launch_hdr(L, display_source(c), c->d_scratch.as<float>(), n);
   CRH_HIP(hipMemcpyAsync(out, c->d_scratch, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
@@ -60,21 +78,11 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   if (c) c->read_since_render = true;
   if (!c || !out || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator / null output");
   CRH_HIP(hipSetDevice(c->device));
-  const uint32_t n = c->par.width * c->par.height;
-  const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
-  const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
-  CRH_HIP(c->d_scratch.reserve(3 * (size_t)n));
-  const uint8_t* d_mask = overlay ? c->d_picked : nullptr;            // written by the device-side tile draw of the last iteration
+  const size_t bytes = 3 * (size_t)c->par.width * c->par.height;
+  CRH_HIP(c->d_scratch.reserve(bytes));
   Launch L{cstream(c), c->grid, false};
-  const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
-  const float* metered = meter_in_front(c, L, src, 0);               // auto exposure meters the UNFILTERED image ...
-  const float4* shown;
-  if (int rc = reproject_src(c, L.stream, src, 0, &shown)) return rc; // ... reprojected display history (crh_reproject.cpp) and ...
-  if (int rc = denoise_src(c, L.stream, shown, 0, &shown)) return rc; // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
-  launch_tonemap(L, shown, c->d_scratch.as<uint8_t>(), n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, d_mask, c->par.width, ts, metered);
-  if (int rc = outline_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // feature lines (crh_outline.cpp): nothing at all while the feature is off
-  if (int rc = overlay_ldr(c, L.stream, c->d_scratch.as<uint8_t>())) return rc;      // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
-  CRH_HIP(hipMemcpyAsync(out, c->d_scratch, 3 * (size_t)n, hipMemcpyDeviceToHost, cstream(c)));
+  if (int rc = enqueue_display_chain(c, L, 0, 0, c->d_scratch.as<uint8_t>())) return rc;
+  CRH_HIP(hipMemcpyAsync(out, c->d_scratch, bytes, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
 }
@@ -107,19 +115,8 @@ static int read_begin(crh_ctx* c, bool hdr)
   CRH_HIP(hipEventRecord(c->rb_fork, c->stream_));
   CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->rb_fork, 0));
   Launch L{c->rb_stream, c->grid, false};
-  const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
-  if (hdr) launch_hdr(L, src, c->d_rb[slot].as<float>(), n);
-  else {
-    const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
-    const bool overlay = c->show_tiles && c->adaptive && c->picked_valid && c->d_picked.cap() >= n_tiles;
-    const float* metered = meter_in_front(c, L, src, 1 + (int)slot);
-    const float4* shown;
-    if (int rc = reproject_src(c, c->rb_stream, src, 1, &shown)) return rc;     // reprojected display history (crh_reproject.cpp); rb_tm below covers its reads too
-    if (int rc = denoise_src(c, c->rb_stream, shown, 1, &shown)) return rc;      // the denoised display (crh_denoise.cpp); rb_tm below covers its read of the accumulator
-    launch_tonemap(L, shown, c->d_rb[slot], n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, overlay ? c->d_picked : nullptr, c->par.width, ts, metered);
-    if (int rc = outline_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // feature lines (crh_outline.cpp)
-    if (int rc = overlay_ldr(c, c->rb_stream, c->d_rb[slot])) return rc;      // hover / selection (crh_pick.cpp)
-  }
+  if (hdr) launch_hdr(L, display_source(c), c->d_rb[slot].as<float>(), n);
+  else if (int rc = enqueue_display_chain(c, L, 1, 1 + (int)slot, c->d_rb[slot])) return rc;      // rb_tm below covers every read of the accumulator, the history and the guide
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipEventRecord(c->rb_tm[slot], c->rb_stream));
   CRH_HIP(hipMemcpyAsync(c->h_rb[slot], c->d_rb[slot], bytes, hipMemcpyDeviceToHost, c->rb_stream));
@@ -209,7 +206,7 @@ int crh_measure_exposure(crh_ctx* c, const crh_meter_params* p, crh_meter_result
   if (int rc = ensure_meter_blocks(c)) return rc;
   CRH_HIP(hipSetDevice(c->device));
   Launch L{cstream(c), c->grid, false};
-  meter_image(c, L, c->assembled_valid ? c->d_assembled : c->d_accum, *p, c->d_meter + 3);
+  meter_image(c, L, display_source(c), *p, c->d_meter + 3);
   CRH_HIP(hipGetLastError());
   DMeter h;
   CRH_HIP(hipMemcpyAsync(&h, c->d_meter + 3, sizeof h, hipMemcpyDeviceToHost, cstream(c)));
@@ -225,7 +222,7 @@ int crh_save_accum(crh_ctx* c, float* out, uint32_t* frames_done)
   if (!c || !out || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator / null output");
   CRH_HIP(hipSetDevice(c->device));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
-  CRH_HIP(hipMemcpyAsync(out, c->assembled_valid ? c->d_assembled : c->d_accum, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, cstream(c)));
+  CRH_HIP(hipMemcpyAsync(out, display_source(c), sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, cstream(c)));
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   if (frames_done) *frames_done = c->frames_done;
   return CRH_OK;

@@ -5,8 +5,6 @@
 // One kernel (reproject_kernels.hip); the rule has ONE copy (reproject_kernels.h), compiled for the kernel and for the host twin below.  Display state: nothing of the
 // rendering state is touched, and only the source of the filter / the tone map changes.  DESIGN.md section 4.13.
 // (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
-#include <new>
-
 #include "crh_context.h"
 #include "reproject_kernels.h"
 
@@ -81,11 +79,7 @@ int reproject_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const 
   if (int rc = ensure_guide(c)) return rc;
   const size_t n = (size_t)c->par.width * c->par.height;
   DevBuf<float4>& out = c->d_rp_out[set];
-  if (out.cap() < n) {
-    // Set 0 is read and written on the context's stream by calls that end with a wait for it: nothing is in flight.  Set 1 belongs to the read-back stream.
-    if (set == 1) CRH_HIP(hipStreamSynchronize(c->rb_stream));
-    CRH_HIP(out.reserve(n));
-  }
+  if (int rc = grow_display_scratch(c, set, &out, 1, n)) return rc;
   resolve(c, on, src, history_of(c), rule_of(c->rp_par), out);
   CRH_HIP(hipGetLastError());
   *shown = out;
@@ -114,9 +108,8 @@ int reproject_capture(crh_ctx* c, const crh_camera* next)
     CRH_HIP(hipStreamSynchronize(cs));                   // first need, or a larger frame: an earlier capture may still be writing the blocks that go
     CRH_HIP(c->d_rp_hist[other].reserve(n)); CRH_HIP(c->d_rp_hguide.reserve(n)); CRH_HIP(c->d_rp_hids.reserve(n));      // (with a valid history the guide copies have this size already)
   }
-  const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
   DScene S; fill_scene(c, S);
-  launch_reproject_resolve(cs, S, c->d_dn_guide, c->d_dn_ids, src, history_of(c), rule_of(c->rp_par), c->d_rp_hist[other]);      // reads the OLD guide copy ...
+  launch_reproject_resolve(cs, S, c->d_dn_guide, c->d_dn_ids, display_source(c), history_of(c), rule_of(c->rp_par), c->d_rp_hist[other]);      // reads the OLD guide copy ...
   CRH_HIP(hipGetLastError());
   CRH_HIP(hipMemcpyAsync(c->d_rp_hguide, c->d_dn_guide, sizeof(float4) * n, hipMemcpyDeviceToDevice, cs));                         // ... which this then replaces
   CRH_HIP(hipMemcpyAsync(c->d_rp_hids, c->d_dn_ids, sizeof(int2) * n, hipMemcpyDeviceToDevice, cs));
@@ -171,7 +164,7 @@ int crh_read_reprojected(crh_ctx* c, float* rgba_out)
   CRH_HIP(hipSetDevice(c->device));
   const float4* shown = nullptr;
   hipStream_t on = cstream(c);
-  if (int rc = reproject_src(c, on, c->assembled_valid ? c->d_assembled : c->d_accum, 0, &shown)) return rc;
+  if (int rc = reproject_src(c, on, display_source(c), 0, &shown)) return rc;
   CRH_HIP(hipMemcpyAsync(rgba_out, shown, sizeof(float4) * (size_t)c->par.width * c->par.height, hipMemcpyDeviceToHost, on));
   CRH_HIP(hipStreamSynchronize(on));
   return CRH_OK;
@@ -192,7 +185,7 @@ int crh_bench_reproject(crh_ctx* c, uint32_t repeats, float* resolve_ms, float* 
   // this call's own blocks, released when it returns: the output image, the capture's guide copies, a stand-in history where there is none
   DevBuf<float4> d_out, d_himg, d_hguide_cp; DevBuf<int2> d_hids_cp;
   CRH_HIP(d_out.reserve(n)); CRH_HIP(d_hguide_cp.reserve(n)); CRH_HIP(d_hids_cp.reserve(n));
-  const float4* src = c->assembled_valid ? c->d_assembled : c->d_accum;
+  const float4* src = display_source(c);
   ReprojectHistory hist = history_of(c);
   if (!hist.valid) {                                     // the current view as its own history: the identity reprojection
     CRH_HIP(d_himg.reserve(n));
@@ -200,28 +193,16 @@ int crh_bench_reproject(crh_ctx* c, uint32_t repeats, float* resolve_ms, float* 
     DScene S; fill_scene(c, S);
     hist.img = d_himg; hist.guide = c->d_dn_guide; hist.ids = c->d_dn_ids; hist.frame = frame_of(S); hist.valid = 1;
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  CRH_HIP(hipEventCreate(&e0));
-  hipError_t e = hipEventCreate(&e1);
-  float ms = 0.f;
-  auto timed = [&](auto&& launch, float* out) {
-    if (e == hipSuccess) e = hipEventRecord(e0, on);
-    for (uint32_t r = 0; r < repeats && e == hipSuccess; ++r) { launch(); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipEventRecord(e1, on);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (out) *out = ms / (float)repeats;
-  };
   resolve(c, on, src, hist, R, d_out);                   // the code is loaded
-  timed([&] { resolve(c, on, src, hist, R, d_out); }, resolve_ms);
-  timed([&] {
+  hipError_t e = time_launches(on, repeats, [&] { resolve(c, on, src, hist, R, d_out); return hipGetLastError(); }, resolve_ms);
+  if (e == hipSuccess) e = time_launches(on, repeats, [&] {
     resolve(c, on, src, hist, R, d_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hguide_cp, c->d_dn_guide, sizeof(float4) * n, hipMemcpyDeviceToDevice, on);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hids_cp, c->d_dn_ids, sizeof(int2) * n, hipMemcpyDeviceToDevice, on);
+    hipError_t ec = hipGetLastError();
+    if (ec == hipSuccess) ec = hipMemcpyAsync(d_hguide_cp, c->d_dn_guide, sizeof(float4) * n, hipMemcpyDeviceToDevice, on);
+    if (ec == hipSuccess) ec = hipMemcpyAsync(d_hids_cp, c->d_dn_ids, sizeof(int2) * n, hipMemcpyDeviceToDevice, on);
+    return ec;
   }, capture_ms);
-  const hipError_t e2 = hipStreamSynchronize(on);        // whatever went wrong: nothing still uses the events and this call's blocks when they go
-  hipEventDestroy(e0); if (e1) hipEventDestroy(e1);
-  CRH_HIP(e); CRH_HIP(e2);
+  CRH_HIP(e);                                            // (time_launches has waited for the stream: this call's blocks may go)
   return CRH_OK;
 }
 
@@ -231,15 +212,10 @@ int crh_reproject_frame_host(const crh_camera* cam, uint32_t width, uint32_t hei
   const float v[] = {cam->eye[0], cam->eye[1], cam->eye[2], cam->dir[0], cam->dir[1], cam->dir[2], cam->up[0], cam->up[1], cam->up[2], cam->fovy_deg, cam->aspect, cam->ortho_scale};
   if (!all_finite(v, sizeof v / sizeof v[0], 1.0e30f)) return CRH_E_INVALID;
   if (!(cam->aspect > 0.f) && (!width || !height)) return CRH_E_INVALID;
-  // right / up / fwd, tan_half and aspect exactly as fill_scene derives them (crh_scene.cpp; crh_fit.cpp restates the same lines)
-  const crh_v3 fwd = crh_norm3(crh_mk3(cam->dir[0], cam->dir[1], cam->dir[2]));
-  const crh_v3 right = crh_norm3(crh_cross3(fwd, crh_mk3(cam->up[0], cam->up[1], cam->up[2])));
-  const crh_v3 up = crh_cross3(right, fwd);
-  float s, cs; crh_sincos((cam->fovy_deg * 0.5f) * (CRH_PI / 180.0f), &s, &cs);
+  const CameraFrame f = camera_frame(*cam, width, height);      // what fill_scene puts into the kernels' DScene
   DScene S{};
-  S.eye = crh_mk3(cam->eye[0], cam->eye[1], cam->eye[2]); S.fwd = fwd; S.right = right; S.up = up;
-  S.tan_half = s / cs;
-  S.aspect = cam->aspect > 0.f ? cam->aspect : (float)width / (float)height;
+  S.eye = crh_mk3(cam->eye[0], cam->eye[1], cam->eye[2]); S.fwd = f.fwd; S.right = f.right; S.up = f.up;
+  S.tan_half = f.tan_half; S.aspect = f.aspect;
   S.ortho_scale = cam->ortho_scale; S.is_ortho = cam->is_ortho;
   *out = frame_of(S);
   return CRH_OK;
@@ -254,10 +230,7 @@ int crh_reproject_host(const float* accum_rgba, const float* rays_px, const int3
   if (params_refused(p)) return CRH_E_INVALID;
   const size_t n = (size_t)width * height;
   std::vector<OutlineTri> tb; std::vector<float4> in, hist, out;      // (the caller's bytes need not be aligned)
-  try { tb.resize(n_tri); in.resize(n); out.resize(n); if (hist_rgba) hist.resize(n); } catch (const std::bad_alloc&) { return CRH_E_NOMEM; }
-  if (n_tri) std::memcpy(tb.data(), table, sizeof(OutlineTri) * (size_t)n_tri);
-  std::memcpy(in.data(), accum_rgba, sizeof(float4) * n);
-  if (hist_rgba) std::memcpy(hist.data(), hist_rgba, sizeof(float4) * n);
+  if (aligned_copy(tb, table, n_tri) || aligned_copy(in, accum_rgba, n) || aligned_copy(out, nullptr, n) || aligned_copy(hist, hist_rgba, hist_rgba ? n : 0)) return CRH_E_NOMEM;
   crh_reproject_frame F{}; if (hist_rgba) F = *hist_cam;
   reproject_host(in.data(), rays_px, object_px, triangle_px, t_px, hist_rgba ? hist.data() : nullptr, hist_object, hist_triangle, hist_t, F, tb.data(), n_tri, width, height,
                  rule_of(*p), out.data());

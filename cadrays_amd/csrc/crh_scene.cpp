@@ -30,12 +30,8 @@ void fill_scene(const crh_ctx* c, DScene& S)
   for (int k = 0; k < 3; ++k) S.bg[k] = c->par.background[k];
   S.env_as_bg = c->par.env_as_background;
   S.eye = crh_mk3(c->cam.eye[0], c->cam.eye[1], c->cam.eye[2]);
-  S.fwd = crh_norm3(crh_mk3(c->cam.dir[0], c->cam.dir[1], c->cam.dir[2]));
-  S.right = crh_norm3(crh_cross3(S.fwd, crh_mk3(c->cam.up[0], c->cam.up[1], c->cam.up[2])));
-  S.up = crh_cross3(S.right, S.fwd);
-  float s, cs; crh_sincos((c->cam.fovy_deg * 0.5f) * (CRH_PI / 180.0f), &s, &cs);
-  S.tan_half = s / cs;
-  S.aspect = c->cam.aspect > 0.f ? c->cam.aspect : (float)c->par.width / (float)c->par.height;
+  const CameraFrame cf = camera_frame(c->cam, c->par.width, c->par.height);
+  S.fwd = cf.fwd; S.right = cf.right; S.up = cf.up; S.tan_half = cf.tan_half; S.aspect = cf.aspect;
   S.ortho_scale = c->cam.ortho_scale; S.aperture = c->cam.aperture_radius; S.focal = c->cam.focal_dist; S.is_ortho = c->cam.is_ortho;
   S.width = c->par.width; S.height = c->par.height; S.max_depth = c->par.max_depth; S.tile_size = c->par.tile_size;
   S.clampv = c->par.radiance_clamp;
@@ -270,7 +266,7 @@ int crh_set_geometry(crh_ctx* c, const float* pos, const float* nrm, const float
   if (uv) c->uv.assign(uv, uv + 2 * (size_t)nV); else c->uv.clear();
   c->tri.assign(tri, tri + 4 * (size_t)nT);
   c->two_level = false; c->nO = 0; c->xf.clear(); c->tri_obj.clear(); c->hidden.clear();      // a new scene: everything displayed
-  clear_selection(c); c->ids_valid = false; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true; c->ol_table_dirty = true;      // ... nothing selected or hovered
+  clear_selection(c); c->ids_valid = false; geometry_changed(c);      // ... nothing selected or hovered; the tables derived from the geometry are stale
   if (tri_obj && xf && nO) {
     // two-level mode: vertices stay in object space; every object gets its own tree (crh_build), the top-level tree
     // over the instances carries the transforms (crh_set_transforms rebuilds only that)
@@ -450,7 +446,7 @@ int crh_add_object(crh_ctx* c, const float* pos, const float* nrm, const float* 
   TwoLevelState::Obj o{}; o.first = T0; o.ntri = nT; o.static0 = false; o.in_static = false;
   c->objs.push_back(o);
   if (!c->hidden.empty()) c->hidden.push_back(0);
-  c->nO = ob + 1; c->pk_tri_obj_dirty = true; c->fit_verts_dirty = true; c->ol_table_dirty = true;
+  c->nO = ob + 1; geometry_changed(c);
   if (object_out) *object_out = ob;
   return apply_objects(c, nullptr, nullptr);
 }
@@ -733,9 +729,7 @@ static int build_scene(crh_ctx* c, const QNode* pre_nodes, uint32_t pre_n_nodes,
   }
   if (c->two_level && !c->hidden.empty()) { if (c->hidden.size() != c->nO) c->hidden.assign(c->nO, 0); if ((rc = apply_objects(c, nullptr, nullptr))) return rc; }      // objects erased before the build: baked like the rest, then disabled
   rc = do_reset(c); if (rc) return rc;
-  c->fit_verts_dirty = true;                             // ... and so does the vertex array of crh_fit_view (crh_fit.cpp)
-  c->ol_table_dirty = true;                              // ... and the per-triangle table of the feature lines (crh_outline.cpp)
-  c->pk_tri_obj_dirty = true;                            // the triangle-to-object table of the id buffer follows the scene (crh_pick.cpp uploads it on first need)
+  geometry_changed(c);                                   // ... and so do the tables derived from the geometry: crh_pick.cpp, crh_fit.cpp, crh_outline.cpp upload theirs on first need
   CRH_HIP(hipStreamSynchronize(cstream(c)));
   return CRH_OK;
 }
