@@ -9,7 +9,9 @@ BOTH sides (CPU oracle here, gfx950 kernels under -m gpu) against exhaustive ray
     is tolerated only where the double-precision hit lies within 1e-5 (barycentric) of a triangle edge, i.e. where float and
     double may legitimately fall on different sides of the edge -- and never on rays that were not aimed at an edge.
 Rays: uniformly random, axis-parallel (with -0.0 components), and rays aimed at triangle edges / vertices +- 1e-6 of the triangle's
-size.  Scene scales 0.01 ... 50; single-level and two-level (per-object transforms) trees.
+size.  Scene scales 0.01 ... 50; scenes without objects, and scenes whose objects carry placements when they are built: crh_build bakes those into
+ONE world-space tree (DESIGN.md section 3 "Two-level scenes"), so both kinds walk a flat tree here.  Objects that are instances -- moved, erased or
+added after the build -- are held to the same truth in tests/test_instance_truth.py.
 """
 import ctypes as C
 import dataclasses
@@ -38,11 +40,14 @@ def bf():
 
 
 def brute_f64(tri_pos, rays):
+    """tri_pos (nT, 9): float32 corners, or float64 ones (placed objects: float vertices under a float matrix, multiplied out in double)"""
     n = len(rays)
     tuv, idx, margin = np.empty((n, 3), np.float64), np.empty(n, np.int32), np.empty(n, np.float64)
-    bf().bf_nearest_f64(tri_pos.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(len(tri_pos)), rays.ctypes.data_as(C.POINTER(C.c_float)),
-                        C.c_uint32(n), tuv.ctypes.data_as(C.POINTER(C.c_double)), idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                        margin.ctypes.data_as(C.POINTER(C.c_double)))
+    assert tri_pos.dtype in (np.float32, np.float64) and tri_pos.flags["C_CONTIGUOUS"] and rays.dtype == np.float32 and rays.flags["C_CONTIGUOUS"]
+    fn, ct = (bf().bf_nearest_f64d, C.c_double) if tri_pos.dtype == np.float64 else (bf().bf_nearest_f64, C.c_float)
+    fn(tri_pos.ctypes.data_as(C.POINTER(ct)), C.c_uint32(len(tri_pos)), rays.ctypes.data_as(C.POINTER(C.c_float)),
+       C.c_uint32(n), tuv.ctypes.data_as(C.POINTER(C.c_double)), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+       margin.ctypes.data_as(C.POINTER(C.c_double)))
     return tuv, idx, margin
 
 
@@ -185,8 +190,9 @@ def test_oracle_walk_equals_exhaustive_tests(oracle_lib, n_tris, seed, scale):
 
 
 def grouped(pos, nrm, tri, n_obj, seed):
-    """the soup cut into n_obj objects (by centroid cell), every object given a rigid / scaled transform; returns the two-level
-    scene and the world-space triangle corners (float64 transform of the object-space vertices)"""
+    """the soup cut into n_obj objects (by centroid cell), every object given a rigid / scaled transform; returns the scene with
+    these placements handed over at build time (crh_build bakes them: no instance) and the world-space triangle corners (float64
+    transform of the object-space vertices)"""
     r = np.random.default_rng(seed)
     cen = pos[tri[:, :3]].mean(1)
     g = int(round(n_obj ** (1 / 3)))
@@ -198,7 +204,7 @@ def grouped(pos, nrm, tri, n_obj, seed):
     world = np.empty((len(tri), 3, 3), np.float64)
     for ob in range(g ** 3):
         a = r.normal(size=3); a /= np.linalg.norm(a)
-        ang = r.random() * 2 * np.pi if ob % 3 else 0.0          # every third object is only translated (the kernel's fast entry)
+        ang = r.random() * 2 * np.pi if ob % 3 else 0.0          # every third object is only translated
         cs, sn = np.cos(ang), np.sin(ang); x, y, z = a
         R = np.array([[cs + x * x * (1 - cs), x * y * (1 - cs) - z * sn, x * z * (1 - cs) + y * sn],
                       [y * x * (1 - cs) + z * sn, cs + y * y * (1 - cs), y * z * (1 - cs) - x * sn],
@@ -212,13 +218,14 @@ def grouped(pos, nrm, tri, n_obj, seed):
     return sc, world
 
 
-def test_oracle_two_level_walk_against_double_precision_truth(oracle_lib):
+def test_oracle_placements_baked_at_build_time_against_double_precision_truth(oracle_lib):
     pos, nrm, tri = soup(3000, 21, 1.0)
     sc, world = grouped(pos, nrm, tri, 27, 5)
     wpos = world.astype(np.float32)
     rays, aimed = make_rays(wpos.reshape(-1, 3), np.arange(3 * len(tri)).reshape(-1, 3), 6000, 22, 1.0)
     o = oracle_lib.Oracle().load_scene(sc)
-    # transforms round differently from the host's double-precision flattening: compare with tolerance only
+    assert o.get_tlas()["n_instances"] == 0                  # one flat tree: the host transformed every vertex once, at the build
+    # the host's flattening of the vertices rounds differently from the float64 one here: compare with tolerance only
     check_against_truth(o.trace_nearest(rays), np.ascontiguousarray(wpos.reshape(-1, 9)), rays, aimed, False)
 
 
@@ -240,11 +247,12 @@ def test_gpu_walk_equals_exhaustive_tests_200k_rays(hip_lib, n_tris, seed, scale
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_obj,seed,scale", [(27, 41, 1.0), (512, 42, 0.05), (64, 43, 20.0)])
-def test_gpu_two_level_walk_against_double_precision_truth(hip_lib, n_obj, seed, scale):
+def test_gpu_placements_baked_at_build_time_against_double_precision_truth(hip_lib, n_obj, seed, scale):
     from cadrays_amd.view import View
     pos, nrm, tri = soup(20000, seed, scale)
     sc, world = grouped(pos, nrm, tri, n_obj, seed)
     wpos = world.astype(np.float32)
     rays, aimed = make_rays(wpos.reshape(-1, 3), np.arange(3 * len(tri)).reshape(-1, 3), 200000, seed + 1, scale)
     v = View(0).load_scene(sc)
+    assert v.get_tlas()["n_instances"] == 0                  # one flat tree (the instance walks: tests/test_instance_truth.py)
     check_against_truth(v.trace_nearest(rays), np.ascontiguousarray(wpos.reshape(-1, 9)), rays, aimed, False)
