@@ -114,6 +114,20 @@ class crh_denoise_params(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("normal_cos", C.c_float), ("depth_ratio", C.c_float), ("until_samples", C.c_uint32)]
 
 
+class crh_shade_guide_params(C.Structure):
+    """the shade guide's parameters (include/cadrays_hip.h; crh_shade_guide_defaults fills them: SHADE_GUIDE_DEFAULTS below)"""
+    _fields_ = [("demodulate", C.c_uint32), ("lights", C.c_uint32), ("albedo_floor", C.c_float), ("light_dilate", C.c_uint32)]
+
+
+class crh_shade_guide_scene(C.Structure):
+    """what crh_shade_guide_host reads of a scene (include/cadrays_hip.h)"""
+    _fields_ = [("mats", C.POINTER(crh_bsdf)), ("texels", C.POINTER(C.c_float)), ("tex_desc", C.POINTER(C.c_uint32)), ("lights", C.POINTER(crh_light)),
+                ("n_mats", C.c_uint32), ("n_texels", C.c_uint32), ("n_tex", C.c_uint32), ("n_lights", C.c_uint32), ("gamma2", C.c_int32)]
+
+
+GUIDE_TABLE_DTYPE = [("uv", "<f4", (3, 2)), ("material", "<i4"), ("has_uv", "<u4")]      # numpy view of the shade guide's per-triangle table (32 B)
+
+
 class crh_reproject_params(C.Structure):
     """the reprojected display history's parameters (include/cadrays_hip.h; crh_reproject_defaults fills them: REPROJECT_DEFAULTS below)"""
     _fields_ = [("max_history", C.c_float), ("until_samples", C.c_uint32), ("normal_cos", C.c_float), ("depth_ratio", C.c_float)]
@@ -135,9 +149,12 @@ OUTLINE_DEFAULTS = dict(kinds=OUTLINE_ALL, crease_cos=_f32(0.8660254037844387), 
 
 DENOISE_DEFAULTS = dict(levels=4, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05), until_samples=256)      # cos 25 deg
 
+SHADE_GUIDE_DEFAULTS = dict(demodulate=1, lights=1, albedo_floor=0.015625, light_dilate=1)      # 1 / 64
+
 REPROJECT_DEFAULTS = dict(max_history=16.0, until_samples=64, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05))      # cos 25 deg
 
 assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
+assert C.sizeof(crh_shade_guide_params) == 16 and C.sizeof(crh_shade_guide_scene) == 56
 assert C.sizeof(crh_reproject_params) == 16 and C.sizeof(crh_reproject_frame) == 64
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
@@ -162,5 +179,7 @@ EXPORTS = [
     "crh_query_region", "crh_region_stats_host", "crh_region_select",
     "crh_outline_defaults", "crh_set_outline", "crh_get_outline", "crh_read_outline", "crh_outline_table_host", "crh_outline_mask_host", "crh_outline_draw_host",
     "crh_denoise_defaults", "crh_set_denoise", "crh_get_denoise", "crh_read_denoised", "crh_denoise_host", "crh_bench_denoise",
+    "crh_shade_guide_defaults", "crh_set_shade_guide", "crh_get_shade_guide", "crh_read_shade_guide", "crh_read_hit_uv", "crh_bench_shade_guide", "crh_guide_table_host",
+    "crh_shade_guide_host", "crh_denoise_guided_host",
     "crh_reproject_defaults", "crh_set_reproject", "crh_get_reproject", "crh_read_reprojected", "crh_bench_reproject", "crh_reproject_frame_host", "crh_reproject_host",
 ]

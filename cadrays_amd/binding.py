@@ -97,9 +97,25 @@ def denoise_params(**fields):
     return _params("denoise", "denoise", fields)
 
 
+def shade_guide_params(**fields):
+    """abi.crh_shade_guide_params: the defaults (abi.SHADE_GUIDE_DEFAULTS == crh_shade_guide_defaults) with the named fields replaced; an unknown name is an error"""
+    return _params("shade_guide", "shade guide", fields)
+
+
 def reproject_params(**fields):
     """abi.crh_reproject_params: the defaults (abi.REPROJECT_DEFAULTS == crh_reproject_defaults) with the named fields replaced; an unknown name is an error"""
     return _params("reproject", "reproject", fields)
+
+
+def pack_lights(lights):
+    """an array of abi.crh_light (at least one entry) of scenes.Light objects, as crh_set_lights takes them"""
+    arr = (abi.crh_light * max(len(lights), 1))()
+    for i, l in enumerate(lights):
+        arr[i].vec[:] = [float(x) for x in l.vec]
+        arr[i].is_point = 1.0 if l.is_point else 0.0
+        arr[i].emission[:] = [float(np.float32(c) * np.float32(l.intensity)) for c in l.color]
+        arr[i].smoothness = float(l.smoothness)
+    return arr
 
 
 class Backend:
@@ -189,13 +205,7 @@ class Backend:
         self._call("set_materials", arr, C.c_uint32(len(bsdfs)))
 
     def set_lights(self, lights):
-        arr = (abi.crh_light * max(len(lights), 1))()
-        for i, l in enumerate(lights):
-            arr[i].vec[:] = [float(x) for x in l.vec]
-            arr[i].is_point = 1.0 if l.is_point else 0.0
-            arr[i].emission[:] = [float(np.float32(c) * np.float32(l.intensity)) for c in l.color]
-            arr[i].smoothness = float(l.smoothness)
-        self._call("set_lights", arr, C.c_uint32(len(lights)))
+        self._call("set_lights", pack_lights(lights), C.c_uint32(len(lights)))
 
     def set_envmap(self, env):
         if env is None:
@@ -506,6 +516,42 @@ class Backend:
         """crh_bench_denoise: dict(guide_ms, pass_ms) -- device time per launch of the guide kernel and of every pass of the parameters in force (HIP events)"""
         g, p = C.c_float(0), (C.c_float * 5)()
         self._call("bench_denoise", C.c_uint32(int(repeats)), C.byref(g), p)
+        return {"guide_ms": float(g.value), "pass_ms": [float(x) for x in p]}
+
+    # -- shade guide of the denoised display: albedo demodulation, lights in view (crh_shade_guide.cpp) --
+    def set_shade_guide(self, on=True, **params):
+        """crh_set_shade_guide: the denoise filter works on the image divided by the first hit's albedo and leaves the pixels that show a positional light alone
+        (fields of crh_shade_guide_params by name, the others take crh_shade_guide_defaults); on=False / None switches it off.  Display state; it shows only while
+        the denoise filter is on, or through read_denoised."""
+        if not on:
+            self._call("set_shade_guide", None)
+            return
+        p = shade_guide_params(**params)
+        self._call("set_shade_guide", C.byref(p))
+
+    def get_shade_guide(self):
+        """crh_get_shade_guide: dict(demodulate, lights, albedo_floor, light_dilate, on) as in force (the defaults while the feature is off)"""
+        p, on = abi.crh_shade_guide_params(), C.c_int(0)
+        self._call("get_shade_guide", C.byref(p), C.byref(on))
+        return {"demodulate": int(p.demodulate), "lights": int(p.lights), "albedo_floor": np.float32(p.albedo_floor), "light_dilate": int(p.light_dilate),
+                "on": bool(on.value)}
+
+    def read_shade_guide(self):
+        """crh_read_shade_guide: (H, W, 4) float32 {1 / albedo rgb, light flag} with the parameters in force (the defaults while the feature is off)"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._call("read_shade_guide", _fp(out))
+        return out
+
+    def read_hit_uv(self):
+        """crh_read_hit_uv: (H, W, 2) float32, the barycentric coordinates of the id buffer's hits (what read_ids leaves out)"""
+        out = np.empty((self.height, self.width, 2), np.float32)
+        self._call("read_hit_uv", _fp(out))
+        return out
+
+    def bench_shade_guide(self, repeats=20):
+        """crh_bench_shade_guide: dict(guide_ms, pass_ms) -- device time per launch of the plane's kernels and of every guided pass of the filter parameters in force"""
+        g, p = C.c_float(0), (C.c_float * 5)()
+        self._call("bench_shade_guide", C.c_uint32(int(repeats)), C.byref(g), p)
         return {"guide_ms": float(g.value), "pass_ms": [float(x) for x in p]}
 
     # -- reprojected display history in front of the denoise filter (crh_reproject.cpp) ------

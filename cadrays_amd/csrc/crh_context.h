@@ -16,6 +16,8 @@
 //   crh_region.cpp     region queries on the id buffer: rectangle / lasso selection, visible objects (region_kernels.hip), the host-only twin
 //   crh_outline.cpp    feature lines on the LDR read-out: object, depth and crease edges from the id buffer (outline_kernels.hip), the host-only twins
 //   crh_denoise.cpp    the denoised display: an id-guided a-trous filter in front of the LDR read-outs' tone map (denoise_kernels.hip), the host-only twin
+//   crh_shade_guide.cpp  the shade guide of the denoised display: per pixel 1 / albedo and "a light shows here", the guided pass (shade_guide_kernels.hip), the
+//                      host-only twins
 //   crh_reproject.cpp  reprojected display history: the image an ending view displayed, blended into the next view's in front of the denoise filter
 //                      (reproject_kernels.hip), the capture in crh_set_camera, the host-only twin
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
@@ -297,6 +299,18 @@ struct DenoiseState {
   bool dn_staged = true;            // steps 1 and 2 take the LDS-staged kernel (denoise_kernels.hip): 67 - 72 against 77 - 85 us per pass at 1080p; CRH_DENOISE_STAGED=0: the plain gather; the same bytes either way
 };
 
+// ---- shade guide of the denoised display (crh_shade_guide.cpp): display state like the filter it serves.  The per-triangle table (32 B: uv of the three vertices,
+// material) is DERIVED from uv / tri and uploaded by the first call that needs it after the geometry changed; the plane (per pixel {1 / albedo, light flag}) and the
+// flag bytes it is dilated from are derived from the id buffer, the table and the SHADING -- materials, textures, lights, spec: shade_gen, bumped by their setters --
+// and kept while none of them, nor the frame size, nor the parameters change.  A host that never switches the feature on pays nothing.
+struct ShadeGuideState {
+  bool sg_on = false; crh_shade_guide_params sg_par{};
+  DevBuf<void> d_sg_table; uint32_t sg_n_tri = 0; uint64_t sg_table_gen = 0;      // (the geom_gen the table was built from)
+  DevBuf<float4> d_sg_plane; DevBuf<uint8_t> d_sg_seen;
+  DerivedStamp sg_stamp; uint64_t sg_stamp_shade = 0;      // what the plane was computed from: par = the parameter bits; the shade_gen
+  uint64_t shade_gen = 1;                                  // THE SHADING GENERATION
+};
+
 // ---- reprojected display history (crh_reproject.cpp): display state like the denoised display -- only the LDR read-outs (and crh_read_reprojected) look at it.  The
 // HISTORY is what crh_set_camera captured of the view that ended: two images (a capture reads one and writes the other), a copy of that view's guide planes, its camera
 // frame.  One output image per SET, as the denoise filter has them: set 0 the context's stream, set 1 the read-back stream.  A host that never switches the feature on
@@ -322,7 +336,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ReprojectState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ShadeGuideState, crh::ReprojectState, crh::TimingState {
   int device = 0;
   uint64_t geom_gen = 1;  // THE GEOMETRY GENERATION: geometry_changed() bumps it; every table derived from pos / tri / tri_obj remembers the one it was built from (0: none yet)
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
@@ -491,6 +505,9 @@ int ensure_ids_and_table(crh_ctx* c);                              // what the o
 // after the metering, which keeps reading `src`.
 int denoise_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown);
 int ensure_guide(crh_ctx* c);      // the guide (d_dn_guide, d_dn_ids) of the state in force, computed if stale; synchronous on the side stream
+// ---- crh_shade_guide.cpp
+int ensure_shade_plane(crh_ctx* c);      // the plane (d_sg_plane) of the state and the parameters in force (the defaults while off), computed if stale; synchronous on the side stream
+inline void shading_changed(crh_ctx* c) { ++c->shade_gen; }      // crh_set_materials, crh_set_texture, crh_set_lights, crh_set_spec -- nowhere else
 // ---- crh_reproject.cpp
 // The image the denoise filter / the tone map of an LDR read-out receives, in *shown: `src` itself while the feature is off, there is no scene or no valid history
 // (nothing is allocated, nothing is launched), else the resolved image of set `set` (0: the context's stream, 1: the read-back stream), enqueued on `on`.  Called just

@@ -6,7 +6,7 @@
 // state is touched, and only the tone map's source changes.  DESIGN.md section 4.12.
 // (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
 #include "crh_context.h"
-#include "denoise_kernels.h"
+#include "shade_guide_kernels.h"      // (includes denoise_kernels.h) the guided pass, taken while crh_set_shade_guide is on
 
 using namespace crh;
 using namespace crh::api;
@@ -40,6 +40,8 @@ DenoiseRule rule_of(const crh_denoise_params& p) { return DenoiseRule{p.levels, 
 int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const DenoiseRule& R, const float4** shown)
 {
   if (int rc = ensure_guide(c)) return rc;
+  const bool guided = c->sg_on;                          // the shade guide (crh_shade_guide.cpp): off -- nothing of it is allocated, nothing launched
+  if (guided) if (int rc = ensure_shade_plane(c)) return rc;
   const uint32_t W = c->par.width, H = c->par.height;
   const size_t n = (size_t)W * H;
   DevBuf<float4>* img = c->d_dn_img[set];
@@ -47,7 +49,8 @@ int filter(crh_ctx* c, hipStream_t on, const float4* src, int set, const Denoise
   const float4* in = src;
   for (uint32_t k = 0; k < R.levels; ++k) {
     float4* out = img[k & 1u];
-    launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged);
+    if (guided) launch_denoise_pass_guided(on, c->d_dn_guide, c->d_dn_ids, c->d_sg_plane, in, out, W, H, k, R);
+    else launch_denoise_pass(on, c->d_dn_guide, c->d_dn_ids, in, out, W, H, k, R, c->dn_staged);
     in = out;
   }
   CRH_HIP(hipGetLastError());

@@ -465,7 +465,7 @@ int crh_set_materials(crh_ctx* c, const crh_bsdf* m, uint32_t n)
   if (!c || (n && !m)) return fail(c, CRH_E_INVALID, "null materials");
   if (!all_finite((const float*)m, 32 * (size_t)n)) return fail(c, CRH_E_INVALID, "material holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
-  c->mats.assign(m, m + n); c->pending_n = 0; reproject_drop(c);
+  c->mats.assign(m, m + n); c->pending_n = 0; reproject_drop(c); shading_changed(c);
   return dev_put(c, c->d_mats, c->mats.data(), sizeof(crh_bsdf) * n, 16 * sizeof(crh_bsdf));
 }
 
@@ -474,7 +474,7 @@ int crh_set_lights(crh_ctx* c, const crh_light* l, uint32_t n)
   if (!c || (n && !l)) return fail(c, CRH_E_INVALID, "null lights");
   if (!all_finite((const float*)l, 8 * (size_t)n, 1.0e30f)) return fail(c, CRH_E_INVALID, "light holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
-  c->lights.assign(l, l + n); c->pending_n = 0; reproject_drop(c);
+  c->lights.assign(l, l + n); c->pending_n = 0; reproject_drop(c); shading_changed(c);
   return upload_lights(c);
 }
 
@@ -511,7 +511,7 @@ int crh_set_texture(crh_ctx* c, uint32_t slot, const float* rgb, uint32_t w, uin
     }
     t.w = w; t.h = h;
   }
-  c->textures_dirty = true; c->pending_n = 0;
+  c->textures_dirty = true; c->pending_n = 0; shading_changed(c);
   return do_reset(c);
 }
 
@@ -547,7 +547,7 @@ int crh_set_spec(crh_ctx* c, const crh_spec* sp)
   if (!c) return CRH_E_INVALID;
   crh_spec n; const char* why = "";
   if (crh_spec_normalise(sp, &n, &why)) return fail(c, CRH_E_INVALID, why);      // an older, shorter struct is accepted: the fields it lacks take their defaults
-  c->spec = n;
+  c->spec = n; shading_changed(c);
   return do_reset(c);                                     // like every rendering-parameter change (pending look-ahead samples are dropped there)
 }
 

@@ -91,12 +91,17 @@ struct DenoisePlanesLds {
 //   is not finite or not similar to p is skipped; otherwise c = h[dy + 2] * h[dx + 2], h = {1, 4, 6, 4, 1}, an integer exact as a float, and per channel
 //   sum = sum + c * in[q]: the product rounded, then the sum rounded.  The centre always counts, so the integer weight sum is >= 36.
 //   OUTPUT: (sum.rgb / (float)weight sum, in[p].w): one plain division per channel.
-template <class Planes> CRH_HD float4 denoise_pixel(const Planes& P, uint32_t x, uint32_t y, uint32_t W, uint32_t H, uint32_t k, const DenoiseRule& R)
+// THE GUIDED FORM (Guided; the shade guide, shade_guide_kernels.h): P also hands out the plane G = {w.r, w.g, w.b, L} by pixel coordinates.  A pixel with G.L != 0
+// passes through, a tap with G.L != 0 is skipped; a tap's channel enters as d = in[q] * G[q].w, rounded, then c * d, rounded, then the sum; the output is
+// (sum / weight sum) / G[p].w: two plain divisions per channel.  A plane of (1, 1, 1, 0) gives the bytes of the unguided form, which is compiled as it was.
+template <bool Guided, class Planes> CRH_HD float4 denoise_pixel_rule(const Planes& P, uint32_t x, uint32_t y, uint32_t W, uint32_t H, uint32_t k, const DenoiseRule& R)
 {
   const float4 a = P.colour(x, y);
   const DenoisePx p = P.at(x, y);
   if (p.triangle < 0 || !(a.w > 0.f) || !denoise_finite3(a)) return a;
   if (!(a.w * (float)(1u << (2u * k)) < R.until)) return a;
+  [[maybe_unused]] float gx = 1.f, gy = 1.f, gz = 1.f;
+  if constexpr (Guided) { const float4 g = P.shade(x, y); if (g.w != 0.f) return a; gx = g.x; gy = g.y; gz = g.z; }
   const int32_t step = (int32_t)(1u << k);
   float sr = 0.f, sg = 0.f, sb = 0.f; uint32_t wsum = 0u;
   for (int32_t dy = -2; dy <= 2; ++dy) {
@@ -109,16 +114,27 @@ template <class Planes> CRH_HD float4 denoise_pixel(const Planes& P, uint32_t x,
       const float4 b = P.colour((uint32_t)qx, (uint32_t)qy);
       if (!(b.w > 0.f) || !denoise_finite3(b)) continue;
       if (!denoise_similar(p, P.at((uint32_t)qx, (uint32_t)qy), R.normal_cos, R.depth_ratio)) continue;
+      float bx = b.x, by = b.y, bz = b.z;
+      if constexpr (Guided) {
+        const float4 g = P.shade((uint32_t)qx, (uint32_t)qy);
+        if (g.w != 0.f) continue;
+        bx = b.x * g.x; by = b.y * g.y; bz = b.z * g.z;
+      }
       const uint32_t c = hy * (dx == 0 ? 6u : ((dx == -1 || dx == 1) ? 4u : 1u));
       const float cf = (float)c;
-      const float pr = cf * b.x, pg = cf * b.y, pb = cf * b.z;
+      const float pr = cf * bx, pg = cf * by, pb = cf * bz;
       sr = sr + pr; sg = sg + pg; sb = sb + pb;
       wsum += c;
     }
   }
   const float ws = (float)wsum;
-  return make_float4(sr / ws, sg / ws, sb / ws, a.w);
+  if constexpr (Guided) return make_float4((sr / ws) / gx, (sg / ws) / gy, (sb / ws) / gz, a.w);
+  else return make_float4(sr / ws, sg / ws, sb / ws, a.w);
 }
+template <class Planes> CRH_HD float4 denoise_pixel(const Planes& P, uint32_t x, uint32_t y, uint32_t W, uint32_t H, uint32_t k, const DenoiseRule& R)
+{ return denoise_pixel_rule<false>(P, x, y, W, H, k, R); }
+template <class Planes> CRH_HD float4 denoise_pixel_guided(const Planes& P, uint32_t x, uint32_t y, uint32_t W, uint32_t H, uint32_t k, const DenoiseRule& R)
+{ return denoise_pixel_rule<true>(P, x, y, W, H, k, R); }
 
 // guide / ids: W * H records each, written for every pixel.  object / hit: the id buffer's planes; table: n_tri records on the device (not read when n_tri == 0).
 void launch_denoise_guide(hipStream_t stream, const int32_t* object, const float4* hit, uint32_t W, uint32_t H, const OutlineTri* table, uint32_t n_tri, float4* guide,

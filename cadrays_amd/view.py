@@ -176,6 +176,20 @@ class View(Backend):
         """(H, W, 4) float32: the image the tone map of an LDR read-out issued now would read, with the parameters in force (the defaults while off)"""
         return self.read_denoised()
 
+    # ---- shade guide of the denoised display (crh_shade_guide.cpp; no counterpart in the reference: OCCT's path tracer shows the raw accumulation) ----
+    def SetShadeGuide(self, demodulate=True, lights=True, albedo_floor=1.0 / 64.0, light_dilate=1):
+        """the denoise filter from now on smooths the image divided by the first hit's albedo (textures and material borders survive) and leaves the disc of a
+        positional light in view alone, grown by light_dilate pixels.  Nothing restarts; it shows while SetDenoise is on."""
+        self.set_shade_guide(True, demodulate=int(bool(demodulate)), lights=int(bool(lights)), albedo_floor=float(albedo_floor), light_dilate=int(light_dilate))
+
+    def ClearShadeGuide(self):
+        """the filter as it is without the guide: the LDR bytes of a view that never called SetShadeGuide"""
+        self.set_shade_guide(False)
+
+    def ReadShadeGuide(self):
+        """(H, W, 4) float32: per pixel 1 / albedo (rgb) and the light flag, with the parameters in force (the defaults while off)"""
+        return self.read_shade_guide()
+
     # ---- reprojected display history (crh_reproject.cpp; no counterpart in the reference: OCCT's path tracer shows the raw accumulation) ----
     def SetReproject(self, max_history=16.0, until_samples=64, normal_deg=25.0, depth_rel=0.05):
         """keep the picture through a camera move: set_camera + reset from now on carry what the ending view displayed over to the next one, blended in with weight up
@@ -503,6 +517,86 @@ def denoise_host(rgba, object_px, triangle_px, t_px, table, **params):
                               C.c_uint32(len(tb)), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc != 0:
         raise BackendError(f"crh_denoise_host -> {rc}")
+    return out
+
+
+def guide_table_host(uv, tri):
+    """crh_guide_table_host on the host only (no GPU): uv (n, 2) float32 per vertex or None (no texture coordinates), tri (m, 4) rows {v0, v1, v2, material}; the
+    shade guide's per-triangle table, a numpy record array of m entries (abi.GUIDE_TABLE_DTYPE, 32 B each)"""
+    lib = load_library()
+    uv = None if uv is None else np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    tri = np.ascontiguousarray(np.asarray(tri).astype(np.int64) & 0xFFFFFFFF, np.uint32).reshape(-1, 4)
+    out = np.zeros(len(tri), abi.GUIDE_TABLE_DTYPE)
+    rc = lib.crh_guide_table_host(None if uv is None else uv.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(0 if uv is None else len(uv)),
+                                  tri.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(len(tri)), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise BackendError(f"crh_guide_table_host -> {rc}")
+    return out
+
+
+def pack_texture_pool(textures):
+    """(texels (n, 4) float32, desc (slots, 4) uint32) of a list of (H, W, 3 | 4) images or None entries, as crh_shade_guide_scene takes them: every slot's
+    RGBA texels back to back (an RGB image gets alpha 1), per slot {first texel, width, height, 0}"""
+    pool, desc, at = [], np.zeros((len(textures), 4), np.uint32), 0
+    for k, im in enumerate(textures):
+        if im is None:
+            continue
+        a = np.asarray(im, np.float32)
+        if a.shape[2] == 3:
+            a = np.concatenate([a, np.ones(a.shape[:2] + (1,), np.float32)], 2)
+        desc[k] = (at, a.shape[1], a.shape[0], 0)
+        pool.append(a.reshape(-1, 4)); at += a.shape[0] * a.shape[1]
+    return (np.ascontiguousarray(np.concatenate(pool), np.float32) if pool else np.zeros((0, 4), np.float32)), desc
+
+
+def shade_guide_host(materials, textures, scene_lights, gamma2, rays, triangle_px, t_px, uv_px, table, **params):
+    """crh_shade_guide_host on the host only (no GPU): materials / scene_lights as Backend.set_materials / set_lights take them, textures a list of (H, W, 3 | 4) images
+    (None: an empty slot), gamma2 = crh_spec's texel_gamma2; rays (H * W, 8) float32 as camera_rays returns them for the pixels in row-major order; the planes as
+    read_ids / read_hit_uv return them; table as guide_table_host returns it; params as in Backend.set_shade_guide; the (H, W, 4) float32 plane read_shade_guide
+    returns"""
+    from .binding import pack_lights, shade_guide_params
+    from .materials import pack_materials
+    lib = load_library()
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    tr, t = np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    uv = np.ascontiguousarray(uv_px, np.float32)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    assert tr.ndim == 2 and tr.shape == t.shape and uv.shape == tr.shape + (2,) and len(r) == tr.size
+    mats = pack_materials(materials)
+    ls = pack_lights(scene_lights)
+    pool, desc = pack_texture_pool(list(textures or []))
+    tb = np.zeros(0, abi.GUIDE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.GUIDE_TABLE_DTYPE)
+    S = abi.crh_shade_guide_scene()
+    S.mats = C.cast(mats, C.POINTER(abi.crh_bsdf)); S.n_mats = len(materials)
+    S.texels = pool.ctypes.data_as(fp) if len(pool) else None; S.n_texels = len(pool)
+    S.tex_desc = desc.ctypes.data_as(C.POINTER(C.c_uint32)) if len(desc) else None; S.n_tex = len(desc)
+    S.lights = C.cast(ls, C.POINTER(abi.crh_light)) if len(scene_lights) else None; S.n_lights = len(scene_lights)
+    S.gamma2 = int(gamma2)
+    p = shade_guide_params(**params)
+    out = np.zeros(tr.shape + (4,), np.float32)
+    rc = lib.crh_shade_guide_host(C.byref(S), r.ctypes.data_as(fp), tr.ctypes.data_as(ip), t.ctypes.data_as(fp), uv.ctypes.data_as(fp), C.c_uint32(tr.shape[1]),
+                                  C.c_uint32(tr.shape[0]), tb.ctypes.data_as(C.c_void_p) if len(tb) else None, C.c_uint32(len(tb)), C.byref(p), out.ctypes.data_as(fp))
+    if rc != 0:
+        raise BackendError(f"crh_shade_guide_host -> {rc}")
+    return out
+
+
+def denoise_guided_host(rgba, object_px, triangle_px, t_px, table, plane, **params):
+    """crh_denoise_guided_host on the host only (no GPU): denoise_host's arguments plus the (H, W, 4) plane as read_shade_guide / shade_guide_host return it"""
+    from .binding import denoise_params
+    lib = load_library()
+    img, sg = np.ascontiguousarray(rgba, np.float32), np.ascontiguousarray(plane, np.float32)
+    ob, tr, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == tr.shape == t.shape and img.shape == sg.shape == ob.shape + (4,)
+    tb = np.zeros(0, abi.OUTLINE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.OUTLINE_TABLE_DTYPE)
+    p = denoise_params(**params)
+    out = np.zeros(img.shape, np.float32)
+    rc = lib.crh_denoise_guided_host(img.ctypes.data_as(C.POINTER(C.c_float)), ob.ctypes.data_as(C.POINTER(C.c_int32)), tr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     t.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]),
+                                     tb.ctypes.data_as(C.c_void_p) if len(tb) else None, C.c_uint32(len(tb)), sg.ctypes.data_as(C.POINTER(C.c_float)), C.byref(p),
+                                     out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise BackendError(f"crh_denoise_guided_host -> {rc}")
     return out
 
 

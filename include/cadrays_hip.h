@@ -598,7 +598,8 @@ CRH_API int crh_outline_draw_host(const uint8_t* mask, uint32_t width, uint32_t 
  *     OUTPUT        out[p] = (sr / (float)Wsum, sg / (float)Wsum, sb / (float)Wsum, in[p].w).  The centre always counts: Wsum >= 36.  The division is the plain a / b.
  *   BINARY edge-stopping weights, INTEGER spline weights; no exp, no fused multiply-add, no atomic, no variance estimate, nothing temporal (reprojection is the next section's, in front of this filter).  Every pixel GATHERS:
  *   nothing is scattered and nothing depends on the order of arrival, so the device, the host twin and a numpy restatement agree bit for bit.
- *   KNOWN LIMITS: diffuse textures are smoothed until the thresholds pass (there is no albedo demodulation); a surface at a grazing angle filters less along the view
+ *   KNOWN LIMITS (the first and the last are what the SHADE GUIDE, the section after this one, repairs when it is switched on): diffuse textures are smoothed until the
+ *   thresholds pass (there is no albedo demodulation in this rule); a surface at a grazing angle filters less along the view
  *   direction (the depth test is a ratio of ray distances, as in the feature lines); an unwelded faceted mesh filters per facet only when normal_cos excludes its
  *   neighbours; at each level's sample threshold the displayed image changes by a small step; a POSITIONAL LIGHT IN VIEW is not in the id buffer -- a light a camera
  *   ray passes replaces the hit in the image only (crh_light) -- so its disc is filtered as part of the surface behind it: dimmed, and smeared over that surface. */
@@ -634,6 +635,93 @@ CRH_API int crh_bench_denoise(crh_ctx* ctx, uint32_t repeats, float* guide_ms, f
  * has no normal.  width, height >= 1; p checked as crh_set_denoise checks it; rgba_out must not overlap rgba; anything else CRH_E_INVALID. */
 CRH_API int crh_denoise_host(const float* rgba, const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height,
                              const void* table, uint32_t n_tri, const crh_denoise_params* p, float* rgba_out /* width*height*4 */);
+
+/* --- shade guide of the denoised display (crh_shade_guide.cpp, cadrays_amd/csrc/shade_guide_kernels.hip) ---------------------------------------------
+ * ALBEDO DEMODULATION and LIGHTS IN VIEW for the filter above.  A per-pixel plane G[p] = {w.r, w.g, w.b, L}, derived from the id buffer like the filter's guide:
+ * w = 1 / albedo of the pixel's first hit -- the filter then smooths colour / albedo, the irradiance, and multiplies the albedo back, so a diffuse texture (rttexture,
+ * AisMesh.cxx:321-346) and a border between two materials of one object survive it -- and L = 1 where a positional light shows (such a light replaces the hit in
+ * the image but not in the id buffer, crh_light): those pixels pass through and no tap is taken from them.  The reference has NO counterpart: OCCT's path tracer
+ * shows the raw accumulation.  Opt-in display state exactly like crh_set_denoise; it has an effect only while the filter is on, or through crh_read_denoised.  Off,
+ * never set, or before crh_build: nothing is allocated, nothing is launched, every byte is what it was.
+ *   TABLE  per CALLER'S triangle index, 32 B: {float u0, v0, u1, v1, u2, v2; int32 material; uint32 has_uv} -- the uv of the triangle's three vertices, the fourth
+ *   word of its row, whether crh_set_geometry got texture coordinates (else the six floats are 0).
+ *   RULE 1, THE PLANE.  Pixel p with the id buffer's record {t, u, v, triangle}.  w = (1, 1, 1) if demodulate == 0 or not 0 <= triangle < n_tri.  Otherwise: mat = the
+ *   record's material, 0 if it is < 0 or >= n_mats; Kd' = Kd.rgb, Kt' = Kt.rgb.  THE TEXTURE BRANCH applies when slot = (int)Kd.w - 1 >= 0, slot < the number of slots
+ *   and the slot is bound, and has_uv: w0 = (1 - u) - v; us = fma(u2, v, fma(u1, u, u0 * w0)) * S, vs likewise from v0 v1 v2 times T (S = Kt.w, T = Le.w, 0 means
+ *   1); a coordinate with !(|c| < 2^22) becomes 0; uf = floor(us), vf = floor(vs) (through (float)(int)c, minus 1 if that lies above c); x = fma(us - uf, W, -0.5),
+ *   y = fma(1 - (vs - vf), H, -0.5); x0 = floor(x), y0 = floor(y), fx = x - x0, fy = y - y0; x0, y0 wrapped into the image by one addition or subtraction of W / H,
+ *   x1 = x0 + 1, y1 = y0 + 1, each 0 when it reaches W / H; per channel (RGBA) tx = lerp(lerp(p00, p10, fx), lerp(p01, p11, fx), fy), lerp(a, b, t) = fma(t, b - a,
+ *   a); with crh_spec texel_gamma2 tx.rgb is squared (one product each; the alpha never).  Then Kd' = Kd * tx.rgb, and if tx.a != 1: Kd' = Kd' * tx.a and
+ *   Kt'_c = fma(tx.a, Kt_c, 1 - tx.a).  This is the renderer's own lookup and cut-out, operation for operation.  Per channel c: m = ((Kd'_c + Ks_c) + Kc_c) + Kt'_c in
+ *   float32, rounded in that order; m not finite -> 1.0f; then !(m >= albedo_floor) -> albedo_floor; w_c = 1.0f / m, the plain division.
+ *   seen[p]: (o, d) = the pixel-centre ray of p, bitwise what crh_camera_rays returns; hd = t[p] if triangle[p] >= 0, else 1e15.  For every light with
+ *   is_point != 0: tl = pos - o; dist = sqrt(dot(tl, tl)) with dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)) (crh_math.h); if dist < hd: q = radius / dist,
+ *   cm = 1.0f / sqrt(fma(q, q, 1.0f)); seen if cm < 1 and dot(d, tl) * (1.0f / dist) >= cm -- what a camera ray sees of the light (crh_light), operation for operation.
+ *   L[p] = 1.0f if lights != 0 and seen[q] for some pixel q of the frame with max(|dx|, |dy|) <= light_dilate, else 0.0f.  (The dilation takes in the edge pixels whose
+ *   centre ray misses the disc while some of their jittered samples hit it.)
+ *   RULE 2, THE GUIDED PASS: the PASS of the denoised display with these changes.  PASS-THROUGH also when G[p].L != 0.  A tap q is also skipped when G[q].L != 0;
+ *   otherwise per channel d = in[q].r * G[q].w.r, then c * d, then sr = sr + that: three rounded float32 operations, no fused multiply-add.  OUTPUT out[p] =
+ *   ((sr / (float)Wsum) / G[p].w.r, likewise g and b, in[p].w): two plain divisions per channel.  Multiplying and dividing by 1.0f are exact, so the plane (1, 1, 1, 0)
+ *   -- demodulate == 0 and lights == 0 -- gives the bytes of the unguided filter.
+ *   STALENESS: the plane is computed by the first read-out that needs it and kept while the id buffer, the table, the frame size, these parameters and the SHADING
+ *   stay what they were; crh_set_materials, crh_set_texture, crh_set_lights and crh_set_spec make it stale.
+ *   KNOWN LIMITS: with crh_set_reproject on as well, the filter passes a light pixel through as the reprojection handed it over, and a history tap taken from a light
+ *   pixel of the old view still ghosts; depth of field widens the displayed disc beyond the pinhole flag (raise light_dilate); the albedo is that of the first hit
+ *   only (what a mirror or a glass pane shows is filtered as before); no shading normals, no variance estimate. */
+typedef struct crh_shade_guide_params {
+  uint32_t demodulate;     /* 0 / 1: divide by the first hit's albedo in front of the filter, multiply back behind it; default 1 */
+  uint32_t lights;         /* 0 / 1: pixels that show a positional light pass through and give no taps; default 1                */
+  float    albedo_floor;   /* in (0, 1], finite: the smallest albedo divided by; default 1/64                                    */
+  uint32_t light_dilate;   /* 0..2 pixels around a flagged pixel centre; default 1                                               */
+} crh_shade_guide_params;  /* 16 B */
+/* what crh_shade_guide_host reads of a scene: the materials as crh_set_materials takes them; every texture slot's RGBA texels back to back (an RGB image stored
+ * with alpha 1; row 0 = top) and per slot four words {first texel, width, height, 0}, width 0 = an empty slot; the lights as crh_set_lights takes them; crh_spec's
+ * texel_gamma2 */
+typedef struct crh_shade_guide_scene {
+  const crh_bsdf*  mats;
+  const float*     texels;      /* 4 * n_texels floats; may be NULL with n_texels == 0 */
+  const uint32_t*  tex_desc;    /* 4 * n_tex words; may be NULL with n_tex == 0        */
+  const crh_light* lights;      /* may be NULL with n_lights == 0                      */
+  uint32_t n_mats, n_texels, n_tex, n_lights;
+  int32_t  gamma2;
+} crh_shade_guide_scene;
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  1, 1, 1/64, 1 */
+CRH_API void crh_shade_guide_defaults(crh_shade_guide_params* p);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  Switch the shade guide on with these parameters, or off with NULL -- the state
+ * of a new context.  Display state: no restart, no work on any stream, allowed before crh_build.  CRH_E_INVALID with a message: demodulate or lights above 1,
+ * albedo_floor outside (0, 1], light_dilate above 2, a NaN or Inf. */
+CRH_API int crh_set_shade_guide(crh_ctx* ctx, const crh_shade_guide_params* p /* NULL = off */);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The parameters in force (the defaults while the feature is off) and whether it
+ * is on; either pointer may be NULL. */
+CRH_API int crh_get_shade_guide(crh_ctx* ctx, crh_shade_guide_params* out, int* on);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The plane of RULE 1 for the state and the parameters in force (the defaults
+ * while the feature is off), W*H*4 floats {w.r, w.g, w.b, L}, row 0 = top.  Synchronous; a stale id buffer or table is computed first, as crh_read_outline does.
+ * Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_read_shade_guide(crh_ctx* ctx, float* plane_out /* W*H*4 */);
+/* the barycentric coordinates (u, v) of the id buffer's hits, W*H*2 floats, row 0 = top -- what crh_read_ids leaves out and crh_pick reports for one pixel; the
+ * values of a miss are not specified.  (No counterpart in the reference: OCCT's selector reports no barycentrics.) */
+CRH_API int crh_read_hit_uv(crh_ctx* ctx, float* uv_out /* W*H*2 */);
+/* Micro-benchmark (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): device time of the plane's kernels (the light test and the
+ * plane itself, together) and of every GUIDED pass of the filter parameters in force (the defaults while off) over the current accumulator, each launched `repeats`
+ * times between two HIP events on the context's stream, in milliseconds per launch.  pass_ms: 5 floats, those beyond `levels` are 0; guide_ms may be NULL.
+ * Synchronous; changes nothing a read-out could see.  Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_bench_shade_guide(crh_ctx* ctx, uint32_t repeats, float* guide_ms, float* pass_ms /* 5 */);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): the TABLE above from uv (2 floats per
+ * vertex; NULL: the geometry has no texture coordinates, n_vertices is not read) and tri (rows of 4 words: v0, v1, v2, material).  CRH_E_INVALID: a null pointer,
+ * n_tri == 0, a vertex index >= n_vertices while uv is given. */
+CRH_API int crh_guide_table_host(const float* uv, uint32_t n_vertices, const uint32_t* tri, uint32_t n_tri, void* table_out /* 32 * n_tri bytes */);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): RULE 1 over caller-supplied planes -- the
+ * same functions the kernels compile, in plain loops, one thread.  rays_px: 8 floats per pixel in crh_camera_rays' layout, row-major; triangle_px, t_px as
+ * crh_read_ids returns them; uv_px as crh_read_hit_uv returns it; guide_table as crh_guide_table_host returns it (may be NULL with n_tri == 0).  CRH_E_INVALID: a
+ * null pointer, width or height 0, parameters crh_set_shade_guide would refuse, a material that holds a NaN / Inf or a texture slot beyond 2^24, a descriptor that
+ * reaches beyond n_texels, n_mats == 0 while n_tri != 0. */
+CRH_API int crh_shade_guide_host(const crh_shade_guide_scene* scene, const float* rays_px, const int32_t* triangle_px, const float* t_px, const float* uv_px,
+                                 uint32_t width, uint32_t height, const void* guide_table, uint32_t n_tri, const crh_shade_guide_params* p,
+                                 float* plane_out /* width*height*4 */);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): all passes of RULE 2 -- crh_denoise_host's
+ * arguments and checks, plus the plane (width*height*4 floats, as crh_read_shade_guide / crh_shade_guide_host return it). */
+CRH_API int crh_denoise_guided_host(const float* rgba, const int32_t* object_px, const int32_t* triangle_px, const float* t_px, uint32_t width, uint32_t height,
+                                    const void* table, uint32_t n_tri, const float* plane, const crh_denoise_params* p, float* rgba_out /* width*height*4 */);
 
 /* --- reprojected display history (crh_reproject.cpp, cadrays_amd/csrc/reproject_kernels.hip) ------------------------------------------------------
  * The application restarts the accumulation on every camera change (AppViewer.cxx:979-984), so during a drag every displayed image has one sample.  With this
