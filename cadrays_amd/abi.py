@@ -139,6 +139,14 @@ class crh_reproject_frame(C.Structure):
                 ("ortho_scale", C.c_float), ("is_ortho", C.c_uint32)]
 
 
+class crh_view_params(C.Structure):
+    """the viewport read-out's parameters (include/cadrays_hip.h; all zero but the size = the whole frame, CRH_VIEW_AUTO: VIEW_DEFAULTS below)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("src", C.c_uint32 * 4), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+VIEW_AUTO, VIEW_NEAREST, VIEW_BILINEAR, VIEW_AREA = 0, 1, 2, 3      # crh_view_params.filter
+VIEW_MAX_SIDE = 8192
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -151,11 +159,14 @@ DENOISE_DEFAULTS = dict(levels=4, normal_cos=_f32(0.9063077870366499), depth_rat
 
 SHADE_GUIDE_DEFAULTS = dict(demodulate=1, lights=1, albedo_floor=0.015625, light_dilate=1)      # 1 / 64
 
+VIEW_DEFAULTS = dict(width=0, height=0, src=(0, 0, 0, 0), filter=VIEW_AUTO, reserved=0)      # (a size must be given)
+
 REPROJECT_DEFAULTS = dict(max_history=16.0, until_samples=64, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05))      # cos 25 deg
 
 assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
 assert C.sizeof(crh_shade_guide_params) == 16 and C.sizeof(crh_shade_guide_scene) == 56
 assert C.sizeof(crh_reproject_params) == 16 and C.sizeof(crh_reproject_frame) == 64
+assert C.sizeof(crh_view_params) == 32
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_region_stats) == 32
@@ -182,4 +193,5 @@ EXPORTS = [
     "crh_shade_guide_defaults", "crh_set_shade_guide", "crh_get_shade_guide", "crh_read_shade_guide", "crh_read_hit_uv", "crh_bench_shade_guide", "crh_guide_table_host",
     "crh_shade_guide_host", "crh_denoise_guided_host",
     "crh_reproject_defaults", "crh_set_reproject", "crh_get_reproject", "crh_read_reprojected", "crh_bench_reproject", "crh_reproject_frame_host", "crh_reproject_host",
+    "crh_read_view", "crh_read_view_begin", "crh_read_view_end", "crh_view_host", "crh_view_fit", "crh_view_to_frame", "crh_bench_view",
 ]

@@ -107,6 +107,11 @@ def reproject_params(**fields):
     return _params("reproject", "reproject", fields)
 
 
+def view_params(**fields):
+    """abi.crh_view_params: the whole frame under CRH_VIEW_AUTO (abi.VIEW_DEFAULTS) with the named fields replaced -- width and height must be; an unknown name is an error"""
+    return _params("view", "view", fields)
+
+
 def pack_lights(lights):
     """an array of abi.crh_light (at least one entry) of scenes.Light objects, as crh_set_lights takes them"""
     arr = (abi.crh_light * max(len(lights), 1))()
@@ -366,6 +371,42 @@ class Backend:
         out = np.empty(shape, np.float32)
         self._call("read_hdr_end", _fp(out))
         return out
+
+    # -- viewport read-out: the frame at the window's size (crh_view.cpp; AppViewer.cxx:929-1102) ------
+    def read_view(self, width, height, src=(0, 0, 0, 0), filter=abi.VIEW_AUTO):
+        """crh_read_view: (height, width, 3) uint8, the frame read_ldr would return resampled to the window's size; src = (x0, y0, x1, y1) half-open in frame
+        pixels (all zero: the whole frame) zooms and pans without a restart; filter: abi.VIEW_AUTO / _NEAREST / _BILINEAR / _AREA"""
+        p = view_params(width=width, height=height, src=src, filter=filter)
+        out = np.empty((p.height, p.width, 3), np.uint8)
+        self._call("read_view", C.byref(p), out.ctypes.data_as(_u8p))
+        return out
+
+    def read_view_begin(self, width, height, src=(0, 0, 0, 0), filter=abi.VIEW_AUTO):
+        """queue display chain + resample + read-back of the frame as submitted so far; returns at once (crh_read_view_begin).  Shares the two slots with
+        read_ldr_begin / read_hdr_begin: the oldest in flight is ended by the call of its own kind"""
+        p = view_params(width=width, height=height, src=src, filter=filter)
+        self._call("read_view_begin", C.byref(p))
+        self._rbv_shapes = getattr(self, "_rbv_shapes", []) + [(p.height, p.width, 3)]
+
+    def read_view_end(self, out=None):
+        """the oldest begun view (crh_read_view_end); `out` as in read_ldr_end, of the shape its read_view_begin asked for"""
+        pending = getattr(self, "_rbv_shapes", None)
+        if not pending and out is None:
+            raise ValueError("read_view_end: no read_view_begin of this object is pending, so the size of the view is not known; pass out=")
+        shape = pending[0] if pending else out.shape
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.dtype != np.uint8 or out.shape != tuple(shape) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError(f"read_view_end(out=...): need a writeable C-contiguous uint8 array of shape {tuple(shape)}")
+        self._call("read_view_end", out.ctypes.data_as(_u8p))
+        if pending: pending.pop(0)
+        return out
+
+    def bench_view(self, width, height, src=(0, 0, 0, 0), filter=abi.VIEW_AUTO, repeats=20):
+        """crh_bench_view: device time per launch of the resample kernel over the frame a read-out issued now would show, in ms (HIP events)"""
+        p, ms = view_params(width=width, height=height, src=src, filter=filter), C.c_float(0)
+        self._call("bench_view", C.byref(p), C.c_uint32(int(repeats)), C.byref(ms))
+        return float(ms.value)
 
     # -- display state and auto exposure (no restart; SettingsWidget.cxx:343-404) -----------
     def set_display(self, tonemap_mode, exposure, white_point):

@@ -20,6 +20,8 @@
 //                      host-only twins
 //   crh_reproject.cpp  reprojected display history: the image an ending view displayed, blended into the next view's in front of the denoise filter
 //                      (reproject_kernels.hip), the capture in crh_set_camera, the host-only twin
+//   crh_view.cpp       the viewport read-out: the finished RGB8 frame resampled to the window's size as the LAST stage of the display chain (view_kernels.hip),
+//                      the letterbox fit, the window-to-frame mapping, the host-only twin
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // Shared by those, below: display_source (the image a read-out shows), grow_display_scratch, geometry_changed / geom_gen and side_upload (the tables derived from the
@@ -232,10 +234,13 @@ struct ScheduleState {
 
 // ---- asynchronous read-back (crh_read_ldr_begin / _end, crh_read_hdr_begin / _end): tone map + device-to-host copy of the frame as submitted so far run on
 // their own stream into one of two device / pinned-host buffer pairs while the next Redraw()s are already rendering; only the NEXT
-// accumulate waits (for the tone map, which reads the accumulator), nothing else does
+// accumulate waits (for the tone map, which reads the accumulator), nothing else does.  A read-back is of one of three KINDS -- the LDR frame, the HDR frame, a view
+// of the LDR frame (crh_view.cpp) -- which share the two slots; the oldest in flight is ended by the call of its own kind.
+enum ReadKind : uint8_t { kReadLdr = 0, kReadHdr = 1, kReadView = 2 };
+struct ViewPlan;      // view_kernels.h
 struct ReadbackState {
   hipStream_t rb_stream = nullptr; hipEvent_t rb_fork = nullptr, rb_tm[2] = {nullptr, nullptr}, rb_done[2] = {nullptr, nullptr};
-  DevBuf<uint8_t> d_rb[2]; PinnedBuf<uint8_t> h_rb[2]; size_t rb_bytes[2] = {0, 0}; bool rb_hdr[2] = {false, false};
+  DevBuf<uint8_t> d_rb[2]; PinnedBuf<uint8_t> h_rb[2]; size_t rb_bytes[2] = {0, 0}; ReadKind rb_kind[2] = {kReadLdr, kReadLdr};
   uint32_t rb_head = 0, rb_outstanding = 0; bool rb_guard_pending = false; hipEvent_t rb_guard = nullptr;
   // auto exposure (crh_set_auto_exposure; kernels in k_meter.h): while on, every LDR read-out meters the image in front of its tone map, on the stream it uses anyway.
   // Four metering blocks (allocated on first need): [0] the synchronous read-out, [1] / [2] the two read-back slots, [3] crh_measure_exposure -- the context's
@@ -326,6 +331,13 @@ struct ReprojectState {
   DevBuf<float4> d_rp_out[2];
 };
 
+// ---- viewport read-out (crh_view.cpp): the full RGB8 frame a view is resampled FROM, one scratch image per SET as the denoise filter has them -- set 0 the context's
+// stream, set 1 the read-back stream, which orders two views in flight by itself.  Nothing else is kept: the parameters travel with every call.  A host that never
+// asks for a view pays nothing.
+struct ViewState {
+  DevBuf<uint8_t> d_vw_full[2];
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -336,7 +348,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ShadeGuideState, crh::ReprojectState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ShadeGuideState, crh::ReprojectState, crh::ViewState, crh::TimingState {
   int device = 0;
   uint64_t geom_gen = 1;  // THE GEOMETRY GENERATION: geometry_changed() bumps it; every table derived from pos / tri / tri_obj remembers the one it was built from (0: none yet)
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
@@ -415,9 +427,9 @@ inline int grow_u32(crh_ctx* c, DevBuf<uint32_t>& d, size_t n)
 // The image a read-out shows: the frame crh_reduce assembled while it is valid, else this context's own accumulator
 inline const float4* display_source(const crh_ctx* c) { return c->assembled_valid ? c->d_assembled : c->d_accum; }
 
-// Room for n pixels in each of the `count` display scratch images at d, which belong to scratch set `set`.  Set 0 is read and written on the context's stream by calls
+// Room for n elements (pixels; bytes of an RGB8 image) in each of the `count` display scratch images at d, which belong to scratch set `set`.  Set 0 is read and written on the context's stream by calls
 // that end with a wait for it: nothing is in flight.  Set 1 belongs to the read-back stream, which is waited for before a block goes.
-inline int grow_display_scratch(crh_ctx* c, int set, DevBuf<float4>* d, int count, size_t n)
+template <class T> int grow_display_scratch(crh_ctx* c, int set, DevBuf<T>* d, int count, size_t n)
 {
   bool room = true;
   for (int k = 0; k < count; ++k) room = room && d[k].cap() >= n;
@@ -522,6 +534,16 @@ inline void reproject_restart(crh_ctx* c)
   if (!keep) c->rp_valid = false;
 }
 inline void reproject_drop(crh_ctx* c) { c->rp_valid = c->rp_fresh = false; }      // the setters that change the picture without a restart of their own
+// ---- crh_readback.cpp
+// THE DISPLAY CHAIN: everything between the image a read-out shows and the RGB8 bytes of the FRAME at d_ldr, enqueued on L.stream (set: the scratch images, block: the
+// metering block).  A view read-out resamples what this wrote (crh_view.cpp): that stage comes last, behind the overlay.
+int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block, uint8_t* d_ldr);
+// the asynchronous read-backs of all three kinds (view: the plan of a kReadView, else NULL) and the end of the oldest one
+int read_begin(crh_ctx* c, ReadKind kind, const ViewPlan* view);
+int read_end(crh_ctx* c, void* out, ReadKind kind);
+// ---- crh_view.cpp
+// The resample of the frame at d_full (W x H of the parameters in force) into d_out, enqueued on `on`
+int view_resample(crh_ctx* c, hipStream_t on, const uint8_t* d_full, const ViewPlan& P, uint8_t* d_out);
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

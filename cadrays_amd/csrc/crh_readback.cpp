@@ -1,6 +1,7 @@
 // crh_readback.cpp -- HDR / LDR read-back (synchronous and asynchronous), accumulator checkpoints, statistics, kernel timing
 // (one of the translation units behind include/cadrays_hip.h; the context, the shared helpers and the map of the files: crh_context.h)
 #include "crh_context.h"
+#include "view_kernels.h"
 
 using namespace crh;
 using namespace crh::api;
@@ -42,7 +43,10 @@ static int ensure_meter_blocks(crh_ctx* c)
 // THE DISPLAY CHAIN: everything between the image a read-out shows and the RGB8 bytes at d_ldr, enqueued on L.stream -- the one place where a
 // display feature is inserted.  `set`: the scratch images of the denoise filter and the reprojection (0: the context's stream, 1: the read-back stream); `block`: the
 // metering block.  The caller owns the stream: nothing here calls cstream().
-static int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block, uint8_t* d_ldr)
+namespace crh {
+namespace api {
+
+int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block, uint8_t* d_ldr)
 {
   const uint32_t n = c->par.width * c->par.height;
   const uint32_t ts = c->par.tile_size, n_tiles = ((c->par.width + ts - 1) / ts) * ((c->par.height + ts - 1) / ts);
@@ -56,6 +60,66 @@ static int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block
   if (int rc = outline_ldr(c, L.stream, d_ldr)) return rc;                // feature lines (crh_outline.cpp): nothing at all while the feature is off
   return overlay_ldr(c, L.stream, d_ldr);                                 // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
 }
+
+// Asynchronous read-back of the frame as submitted so far -- LDR (tone-mapped RGB8), HDR (linear float RGB) or a VIEW of the LDR frame (crh_view.cpp: the frame goes
+// to the scratch image of set 1 and the slot receives its resample): display chain / unpack + device-to-host copy run on a stream of their own into one of two
+// device / pinned-host buffer pairs while the next Redraw()s are already rendering; only the NEXT accumulate waits (for the kernels that read the accumulator: rb_tm
+// is recorded BEHIND the chain and IN FRONT of a view's resample, which reads the scratch image only), nothing else does.
+int read_begin(crh_ctx* c, ReadKind kind, const ViewPlan* view)
+{
+  if (!c || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
+  if (c->rb_outstanding >= 2) return fail(c, CRH_E_INVALID, "two read-backs are already in flight (crh_read_ldr_end / crh_read_hdr_end / crh_read_view_end first)");
+  CRH_HIP(hipSetDevice(c->device));
+  const uint32_t n = c->par.width * c->par.height;
+  const bool resample = kind == kReadView && view && !view->identity;
+  const size_t bytes = resample ? 3 * (size_t)view->X.v * view->Y.v : (kind == kReadHdr ? 12 : 3) * (size_t)n;
+  if (!c->rb_stream) {
+    CRH_HIP(hipStreamCreateWithFlags(&c->rb_stream, hipStreamNonBlocking));
+    CRH_HIP(hipEventCreateWithFlags(&c->rb_fork, hipEventDisableTiming));
+    for (int k = 0; k < 2; ++k) { CRH_HIP(hipEventCreateWithFlags(&c->rb_tm[k], hipEventDisableTiming)); CRH_HIP(hipEventCreateWithFlags(&c->rb_done[k], hipEventDisableTiming)); }
+  }
+  if (bytes > c->d_rb[0].cap() || bytes > c->h_rb[0].cap() || bytes > c->d_rb[1].cap() || bytes > c->h_rb[1].cap()) {
+    CRH_HIP(hipStreamSynchronize(c->rb_stream));
+    if (c->rb_outstanding) return fail(c, CRH_E_INVALID, "the read-back buffers must grow while a read-back is in flight (crh_read_*_end first)");
+    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].release()); CRH_HIP(c->h_rb[k].release()); }
+    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].reserve(bytes)); CRH_HIP(c->h_rb[k].reserve(bytes)); }
+  }
+  if (resample) if (int rc = grow_display_scratch(c, 1, &c->d_vw_full[1], 1, 3 * (size_t)n)) return rc;
+  const uint32_t slot = c->rb_head & 1u;
+  // everything submitted so far comes first: the frames in flight on the pipeline streams (not joined, they stay in flight) and
+  // whatever sits on the context's stream
+  for (int k = 0; k < 8; ++k) if (c->pipe.pipe_pending[k]) CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->lane_join[k], 0));
+  CRH_HIP(hipEventRecord(c->rb_fork, c->stream_));
+  CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->rb_fork, 0));
+  Launch L{c->rb_stream, c->grid, false};
+  if (kind == kReadHdr) launch_hdr(L, display_source(c), c->d_rb[slot].as<float>(), n);
+  else if (int rc = enqueue_display_chain(c, L, 1, 1 + (int)slot, resample ? c->d_vw_full[1] : c->d_rb[slot])) return rc;      // rb_tm below covers every read of the accumulator, the history and the guide
+  CRH_HIP(hipGetLastError());
+  CRH_HIP(hipEventRecord(c->rb_tm[slot], c->rb_stream));
+  if (resample) if (int rc = view_resample(c, c->rb_stream, c->d_vw_full[1], *view, c->d_rb[slot])) return rc;
+  CRH_HIP(hipMemcpyAsync(c->h_rb[slot], c->d_rb[slot], bytes, hipMemcpyDeviceToHost, c->rb_stream));
+  CRH_HIP(hipEventRecord(c->rb_done[slot], c->rb_stream));
+  c->rb_bytes[slot] = bytes; c->rb_kind[slot] = kind;
+  c->rb_guard = c->rb_tm[slot]; c->rb_guard_pending = true;
+  ++c->rb_head; ++c->rb_outstanding;
+  return CRH_OK;
+}
+
+int read_end(crh_ctx* c, void* out, ReadKind kind)
+{
+  if (!c || !out) return fail(c, CRH_E_INVALID, "null output");
+  if (!c->rb_outstanding) return fail(c, CRH_E_INVALID, "no read-back in flight (crh_read_*_begin first)");
+  CRH_HIP(hipSetDevice(c->device));
+  const uint32_t slot = (c->rb_head - c->rb_outstanding) & 1u;          // the oldest one
+  if (c->rb_kind[slot] != kind) return fail(c, CRH_E_INVALID, "the oldest read-back in flight is of another kind (LDR / HDR / view): end it with its own call");
+  CRH_HIP(hipEventSynchronize(c->rb_done[slot]));
+  std::memcpy(out, c->h_rb[slot], c->rb_bytes[slot]);
+  --c->rb_outstanding;
+  return CRH_OK;
+}
+
+}  // namespace api
+}  // namespace crh
 
 extern "C" {
 
@@ -87,63 +151,10 @@ int crh_read_ldr(crh_ctx* c, uint8_t* out)
   return CRH_OK;
 }
 
-// Asynchronous read-back of the frame as submitted so far, LDR (tone-mapped RGB8) or HDR (linear float RGB): tone map / unpack + device-to-host copy
-// run on a stream of their own into one of two device / pinned-host buffer pairs while the next Redraw()s are already rendering; only the NEXT
-// accumulate waits (for the kernel that reads the accumulator), nothing else does.
-static int read_begin(crh_ctx* c, bool hdr)
-{
-  if (!c || !c->d_accum) return fail(c, CRH_E_INVALID, "no accumulator");
-  if (c->rb_outstanding >= 2) return fail(c, CRH_E_INVALID, "two read-backs are already in flight (crh_read_ldr_end / crh_read_hdr_end first)");
-  CRH_HIP(hipSetDevice(c->device));
-  const uint32_t n = c->par.width * c->par.height;
-  const size_t bytes = (hdr ? 12 : 3) * (size_t)n;
-  if (!c->rb_stream) {
-    CRH_HIP(hipStreamCreateWithFlags(&c->rb_stream, hipStreamNonBlocking));
-    CRH_HIP(hipEventCreateWithFlags(&c->rb_fork, hipEventDisableTiming));
-    for (int k = 0; k < 2; ++k) { CRH_HIP(hipEventCreateWithFlags(&c->rb_tm[k], hipEventDisableTiming)); CRH_HIP(hipEventCreateWithFlags(&c->rb_done[k], hipEventDisableTiming)); }
-  }
-  if (bytes > c->d_rb[0].cap() || bytes > c->h_rb[0].cap() || bytes > c->d_rb[1].cap() || bytes > c->h_rb[1].cap()) {
-    CRH_HIP(hipStreamSynchronize(c->rb_stream));
-    if (c->rb_outstanding) return fail(c, CRH_E_INVALID, "the read-back buffers must grow while a read-back is in flight (crh_read_*_end first)");
-    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].release()); CRH_HIP(c->h_rb[k].release()); }
-    for (int k = 0; k < 2; ++k) { CRH_HIP(c->d_rb[k].reserve(bytes)); CRH_HIP(c->h_rb[k].reserve(bytes)); }
-  }
-  const uint32_t slot = c->rb_head & 1u;
-  // everything submitted so far comes first: the frames in flight on the pipeline streams (not joined, they stay in flight) and
-  // whatever sits on the context's stream
-  for (int k = 0; k < 8; ++k) if (c->pipe.pipe_pending[k]) CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->lane_join[k], 0));
-  CRH_HIP(hipEventRecord(c->rb_fork, c->stream_));
-  CRH_HIP(hipStreamWaitEvent(c->rb_stream, c->rb_fork, 0));
-  Launch L{c->rb_stream, c->grid, false};
-  if (hdr) launch_hdr(L, display_source(c), c->d_rb[slot].as<float>(), n);
-  else if (int rc = enqueue_display_chain(c, L, 1, 1 + (int)slot, c->d_rb[slot])) return rc;      // rb_tm below covers every read of the accumulator, the history and the guide
-  CRH_HIP(hipGetLastError());
-  CRH_HIP(hipEventRecord(c->rb_tm[slot], c->rb_stream));
-  CRH_HIP(hipMemcpyAsync(c->h_rb[slot], c->d_rb[slot], bytes, hipMemcpyDeviceToHost, c->rb_stream));
-  CRH_HIP(hipEventRecord(c->rb_done[slot], c->rb_stream));
-  c->rb_bytes[slot] = bytes; c->rb_hdr[slot] = hdr;
-  c->rb_guard = c->rb_tm[slot]; c->rb_guard_pending = true;
-  ++c->rb_head; ++c->rb_outstanding;
-  return CRH_OK;
-}
-
-static int read_end(crh_ctx* c, void* out, bool hdr)
-{
-  if (!c || !out) return fail(c, CRH_E_INVALID, "null output");
-  if (!c->rb_outstanding) return fail(c, CRH_E_INVALID, "no read-back in flight (crh_read_*_begin first)");
-  CRH_HIP(hipSetDevice(c->device));
-  const uint32_t slot = (c->rb_head - c->rb_outstanding) & 1u;          // the oldest one
-  if (c->rb_hdr[slot] != hdr) return fail(c, CRH_E_INVALID, "the oldest read-back in flight is of the other kind (LDR / HDR): end it with its own call");
-  CRH_HIP(hipEventSynchronize(c->rb_done[slot]));
-  std::memcpy(out, c->h_rb[slot], c->rb_bytes[slot]);
-  --c->rb_outstanding;
-  return CRH_OK;
-}
-
-int crh_read_ldr_begin(crh_ctx* c) { return read_begin(c, false); }
-int crh_read_ldr_end(crh_ctx* c, uint8_t* out) { return read_end(c, out, false); }
-int crh_read_hdr_begin(crh_ctx* c) { return read_begin(c, true); }
-int crh_read_hdr_end(crh_ctx* c, float* out) { return read_end(c, out, true); }
+int crh_read_ldr_begin(crh_ctx* c) { return read_begin(c, kReadLdr, nullptr); }
+int crh_read_ldr_end(crh_ctx* c, uint8_t* out) { return read_end(c, out, kReadLdr); }
+int crh_read_hdr_begin(crh_ctx* c) { return read_begin(c, kReadHdr, nullptr); }
+int crh_read_hdr_end(crh_ctx* c, float* out) { return read_end(c, out, kReadHdr); }
 
 // ---- display state without a restart, auto exposure (reference: the exposure / white point sliders and the tone-mapping combo only write fields the display pass
 // reads, SettingsWidget.cxx:343-404).  None of these calls do_reset.

@@ -647,6 +647,46 @@ def reproject_host(accum, rays, object_px, triangle_px, t_px, history, table, **
     return out
 
 
+def view_host(ldr, width, height, src=(0, 0, 0, 0), filter=abi.VIEW_AUTO):
+    """crh_view_host on the host only (no GPU): the (H, W, 3) uint8 frame read_ldr returns, resampled to (height, width, 3) by the rule of read_view -- what a host
+    without the device-side view has to do with every frame it shows"""
+    from .binding import view_params
+    lib = load_library()
+    img = np.ascontiguousarray(ldr, np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3
+    p = view_params(width=width, height=height, src=src, filter=filter)
+    out = np.zeros((p.height, p.width, 3), np.uint8)
+    u8 = C.POINTER(C.c_uint8)
+    rc = lib.crh_view_host(img.ctypes.data_as(u8), C.c_uint32(img.shape[1]), C.c_uint32(img.shape[0]), C.byref(p), out.ctypes.data_as(u8))
+    if rc != 0:
+        raise BackendError(f"crh_view_host -> {rc}")
+    return out
+
+
+def view_fit(frame_w, frame_h, area_w, area_h):
+    """crh_view_fit on the host only (no GPU): the letterbox of AppViewer.cxx:930-953 -- dict(width, height, src, filter), the keyword arguments of read_view for a
+    frame_w x frame_h frame shown whole in a panel of area_w x area_h"""
+    lib = load_library()
+    p = abi.crh_view_params()
+    rc = lib.crh_view_fit(C.c_uint32(int(frame_w)), C.c_uint32(int(frame_h)), C.c_uint32(int(area_w)), C.c_uint32(int(area_h)), C.byref(p))
+    if rc != 0:
+        raise BackendError(f"crh_view_fit -> {rc}")
+    return dict(width=int(p.width), height=int(p.height), src=tuple(int(x) for x in p.src), filter=int(p.filter))
+
+
+def view_to_frame(frame_w, frame_h, vx, vy, width, height, src=(0, 0, 0, 0), filter=abi.VIEW_AUTO):
+    """crh_view_to_frame on the host only (no GPU): the frame pixel (fx, fy) under pixel (vx, vy) of the view these parameters describe -- what pick, set_hover and
+    query_region are to be asked about"""
+    from .binding import view_params
+    lib = load_library()
+    p = view_params(width=width, height=height, src=src, filter=filter)
+    fx, fy = C.c_uint32(0), C.c_uint32(0)
+    rc = lib.crh_view_to_frame(C.byref(p), C.c_uint32(int(frame_w)), C.c_uint32(int(frame_h)), C.c_uint32(int(vx)), C.c_uint32(int(vy)), C.byref(fx), C.byref(fy))
+    if rc != 0:
+        raise BackendError(f"crh_view_to_frame -> {rc}")
+    return int(fx.value), int(fy.value)
+
+
 def build_bvh_host(pos, tri, threads=0):
     """Run the product's BVH builder on the host only (no GPU): returns (nodes[n,16] u32-as-f32, prim_order[nT] u32)."""
     lib = load_library()

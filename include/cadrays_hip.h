@@ -811,6 +811,63 @@ CRH_API int crh_reproject_host(const float* accum_rgba, const float* rays_px, co
                                const float* hist_rgba, const int32_t* hist_object, const int32_t* hist_triangle, const float* hist_t, const crh_reproject_frame* hist_cam,
                                const void* table, uint32_t n_tri, uint32_t width, uint32_t height, const crh_reproject_params* p, float* rgba_out /* width*height*4 */);
 
+/* --- viewport read-out (crh_view.cpp, cadrays_amd/csrc/view_kernels.hip) ------------------------------------------------------------------------
+ * The application renders into a target whose size the user sets apart from the window's ("Resolution" panel, SettingsWidget.cxx:104-149, 128 .. 2048 px per
+ * side), letterboxes it into the panel (AppViewer.cxx:929-957) and draws the FBO's GL_RGB8 colour texture at the panel's size (AppViewer.cxx:1095-1102): the GL
+ * texture unit scales the ENCODED bytes.  These calls do that scaling on the device as the LAST stage of the display chain -- behind tone map, ShowSamplingTiles
+ * outline, feature lines, selection and hover -- so that the host receives the window's bytes, not the frame's; a source rectangle gives zoom and pan on the
+ * accumulated frame.  NOTHING restarts: none of these calls touches the accumulator, the frame counter, the id buffer or crh_stats.
+ *   ARITHMETIC: integers only, exact; the device, the host twin and a numpy restatement agree bit for bit.
+ *   INPUT   the finished RGB8 frame W x H; a source rectangle [x0,x1) x [y0,y1) inside it, sw x sh; an output size vw x vh; a filter.
+ *   PER AXIS, with s source pixels, v output pixels and the rectangle's offset off: output index i has taps (frame index, integer weight), the weights sum to D.
+ *     AREA      lo = i s, hi = (i + 1) s; k from lo div v to (hi - 1) div v; weight min((k + 1) v, hi) - max(k v, lo); index off + k; D = s.
+ *     BILINEAR  n = (2 i + 1) s - v; k0 = floor(n / 2 v) (n may be negative); f = n - k0 2 v; taps (off + k0, 2 v - f) and (off + k0 + 1, f); the indices are
+ *               clamped to the FRAME [0, S - 1], not to the rectangle: the pixels just outside a zoom rectangle are real pixels; D = 2 v.
+ *     NEAREST   one tap off + ((2 i + 1) s) div (2 v), weight 1; D = 1.
+ *     AUTO      per axis: AREA where s >= v, else BILINEAR.
+ *   PER PIXEL each channel is (sum_y w_y sum_x w_x byte + (Dx Dy) div 2) div (Dx Dy), in 64 bits, the exact quotient.
+ *   No filtering in linear light: the reference filters the encoded bytes too.  Lines drawn one frame pixel wide thin out under minification. */
+#define CRH_VIEW_AUTO     0u
+#define CRH_VIEW_NEAREST  1u
+#define CRH_VIEW_BILINEAR 2u
+#define CRH_VIEW_AREA     3u
+#define CRH_VIEW_MAX_SIDE 8192u
+typedef struct crh_view_params {
+  uint32_t width, height;  /* of the image written, 1 .. 8192 each                                                    */
+  uint32_t src[4];         /* x0, y0, x1, y1 half-open, in frame pixels; all zero = the whole frame                    */
+  uint32_t filter;         /* CRH_VIEW_AUTO 0 (the default), _NEAREST 1, _BILINEAR 2, _AREA 3                          */
+  uint32_t reserved;       /* 0                                                                                        */
+} crh_view_params;         /* 32 B */
+/* (reference: the panel's ImGui::Image of the colour texture, AppViewer.cxx:1095-1102)  The frame a crh_read_ldr issued now would return, resampled by the rule
+ * above: width*height*3 bytes, row 0 = top.  Synchronous, on the context's stream.  Identity parameters (the view has the frame's size, the rectangle is the whole
+ * frame, any filter) launch no resample kernel and return crh_read_ldr's bytes.  CRH_E_INVALID with a message: a null pointer; a side of the view of 0 or above
+ * 8192, a frame side above 8192; a rectangle that is empty or leaves the frame IN FORCE (one that was valid before a crh_set_params resize included); filter > 3;
+ * reserved != 0; no accumulator. */
+CRH_API int crh_read_view(crh_ctx* ctx, const crh_view_params* p, uint8_t* rgb_out /* width*height*3 */);
+/* (reference: AppViewer.cxx:1095-1102, one image per GUI frame)  The asynchronous form, as crh_read_ldr_begin / _end: the view of the frame as submitted so far.
+ * It shares the two read-back slots with the LDR and the HDR kind: at most two read-backs of any kind in flight, they come back in order, and the oldest in flight
+ * is ended by the call of its own kind (CRH_E_INVALID otherwise).  _end writes the width*height*3 bytes of the parameters its _begin was given.  The slot buffers
+ * grow to the largest read-back so far and cannot grow while one is in flight.  The next accumulate waits for the display chain, as after crh_read_ldr_begin, not
+ * for the resample.  The refusals of crh_read_view, and two read-backs in flight. */
+CRH_API int crh_read_view_begin(crh_ctx* ctx, const crh_view_params* p);
+CRH_API int crh_read_view_end(crh_ctx* ctx, uint8_t* rgb_out /* width*height*3 of the oldest begin */);
+/* Host-only, no device and no context (reference: the texture unit's scaling, AppViewer.cxx:1095-1102): the rule above over a caller-supplied frame -- the same
+ * functions the kernels compile, in a plain loop, one thread.  out must not overlap ldr.  CRH_E_INVALID: what crh_read_view refuses of p, W and H; a null pointer. */
+CRH_API int crh_view_host(const uint8_t* ldr, uint32_t W, uint32_t H, const crh_view_params* p, uint8_t* out /* p->width*p->height*3 */);
+/* Host-only (reference: the letterbox of AppViewer.cxx:930-935 with the truncation of :952-953, in float32 as written there): the view of a W x H frame in a panel
+ * of area_w x area_h.  aspect = (float)W / (float)H; if (float)area_w / (float)area_h < aspect: width = area_w, height = (uint32_t)((float)area_w / aspect); else
+ * width = (uint32_t)((float)area_h * aspect), height = area_h; each at least 1.  The source is the whole frame, the filter CRH_VIEW_AUTO.  CRH_E_INVALID: a null
+ * pointer, one of the four sides 0 or above 8192. */
+CRH_API int crh_view_fit(uint32_t W, uint32_t H, uint32_t area_w, uint32_t area_h, crh_view_params* out);
+/* Host-only (reference: the panel's mouse position is scaled back to the target, AppViewer.cxx:929-957): the frame pixel under view pixel (vx, vy) -- the NEAREST tap
+ * of both axes -- which is what crh_pick, crh_set_hover and crh_query_region are to be asked about.  CRH_E_INVALID: what crh_read_view refuses of p, W and H; a null
+ * pointer; vx >= p->width or vy >= p->height. */
+CRH_API int crh_view_to_frame(const crh_view_params* p, uint32_t W, uint32_t H, uint32_t vx, uint32_t vy, uint32_t* fx, uint32_t* fy);
+/* Micro-benchmark (reference: the texture unit's scaling, AppViewer.cxx:1095-1102, costs the reference nothing it reports): device time of the resample kernel over
+ * the frame a read-out issued now would show, `repeats` launches between two HIP events on the context's stream, in milliseconds per launch.  The kernel runs for
+ * identity parameters too (a copy).  Synchronous; changes nothing a read-out could see.  The refusals of crh_read_view, and repeats == 0. */
+CRH_API int crh_bench_view(crh_ctx* ctx, const crh_view_params* p, uint32_t repeats, float* resample_ms);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
