@@ -139,6 +139,14 @@ class crh_reproject_frame(C.Structure):
                 ("ortho_scale", C.c_float), ("is_ortho", C.c_uint32)]
 
 
+class crh_reproject_motion_params(C.Structure):
+    """the per-object history deltas' caps (include/cadrays_hip.h; crh_reproject_motion_defaults fills them: REPROJECT_MOTION_DEFAULTS below)"""
+    _fields_ = [("max_history_moved", C.c_float), ("max_history_static", C.c_float)]
+
+
+REPROJECT_DELTA_DTYPE = [("D", "<f4", (12,)), ("flag", "<u4"), ("pad", "<u4", (3,))]      # numpy view of the delta table's records (crh_reproject_delta, 64 B)
+
+
 class crh_view_params(C.Structure):
     """the viewport read-out's parameters (include/cadrays_hip.h; all zero but the size = the whole frame, CRH_VIEW_AUTO: VIEW_DEFAULTS below)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("src", C.c_uint32 * 4), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
@@ -163,9 +171,12 @@ VIEW_DEFAULTS = dict(width=0, height=0, src=(0, 0, 0, 0), filter=VIEW_AUTO, rese
 
 REPROJECT_DEFAULTS = dict(max_history=16.0, until_samples=64, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05))      # cos 25 deg
 
+REPROJECT_MOTION_DEFAULTS = dict(max_history_moved=16.0, max_history_static=8.0)
+
 assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
 assert C.sizeof(crh_shade_guide_params) == 16 and C.sizeof(crh_shade_guide_scene) == 56
 assert C.sizeof(crh_reproject_params) == 16 and C.sizeof(crh_reproject_frame) == 64
+assert C.sizeof(crh_reproject_motion_params) == 8
 assert C.sizeof(crh_view_params) == 32
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
@@ -193,5 +204,6 @@ EXPORTS = [
     "crh_shade_guide_defaults", "crh_set_shade_guide", "crh_get_shade_guide", "crh_read_shade_guide", "crh_read_hit_uv", "crh_bench_shade_guide", "crh_guide_table_host",
     "crh_shade_guide_host", "crh_denoise_guided_host",
     "crh_reproject_defaults", "crh_set_reproject", "crh_get_reproject", "crh_read_reprojected", "crh_bench_reproject", "crh_reproject_frame_host", "crh_reproject_host",
+    "crh_reproject_motion_defaults", "crh_set_reproject_motion", "crh_get_reproject_motion", "crh_get_reproject_launches", "crh_bench_reproject_motion", "crh_reproject_delta_host", "crh_reproject_motion_host",
     "crh_read_view", "crh_read_view_begin", "crh_read_view_end", "crh_view_host", "crh_view_fit", "crh_view_to_frame", "crh_bench_view",
 ]

@@ -107,6 +107,11 @@ def reproject_params(**fields):
     return _params("reproject", "reproject", fields)
 
 
+def reproject_motion_params(**fields):
+    """abi.crh_reproject_motion_params: the defaults (abi.REPROJECT_MOTION_DEFAULTS == crh_reproject_motion_defaults) with the named fields replaced; an unknown name is an error"""
+    return _params("reproject_motion", "reproject motion", fields)
+
+
 def view_params(**fields):
     """abi.crh_view_params: the whole frame under CRH_VIEW_AUTO (abi.VIEW_DEFAULTS) with the named fields replaced -- width and height must be; an unknown name is an error"""
     return _params("view", "view", fields)
@@ -623,6 +628,33 @@ class Backend:
         r, k = C.c_float(0), C.c_float(0)
         self._call("bench_reproject", C.c_uint32(int(repeats)), C.byref(r), C.byref(k))
         return {"resolve_ms": float(r.value), "capture_ms": float(k.value)}
+
+    def set_reproject_motion(self, on=True, **params):
+        """crh_set_reproject_motion: with set_reproject on as well, set_transforms captures and keeps the history, and a moved object's history follows it (fields of
+        crh_reproject_motion_params by name, the others take crh_reproject_motion_defaults); on=False / None switches it off.  Display state."""
+        if not on:
+            self._call("set_reproject_motion", None)
+            return
+        p = reproject_motion_params(**params)
+        self._call("set_reproject_motion", C.byref(p))
+
+    def get_reproject_motion(self):
+        """crh_get_reproject_motion: dict(max_history_moved, max_history_static, on, n_flagged) as in force (the defaults while the feature is off)"""
+        p, on, n = abi.crh_reproject_motion_params(), C.c_int(0), C.c_uint32(0)
+        self._call("get_reproject_motion", C.byref(p), C.byref(on), C.byref(n))
+        return {"max_history_moved": np.float32(p.max_history_moved), "max_history_static": np.float32(p.max_history_static), "on": bool(on.value), "n_flagged": int(n.value)}
+
+    def get_reproject_launches(self):
+        """crh_get_reproject_launches: dict(plain, motion) -- launches of k_reproject_resolve / k_reproject_resolve_motion by read-outs and captures so far"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._call("get_reproject_launches", C.byref(a), C.byref(b))
+        return {"plain": int(a.value), "motion": int(b.value)}
+
+    def bench_reproject_motion(self, repeats=20):
+        """crh_bench_reproject_motion: dict(resolve_ms) -- device time per launch of k_reproject_resolve_motion with the table in force (or the all-flagged stand-in)"""
+        r = C.c_float(0)
+        self._call("bench_reproject_motion", C.c_uint32(int(repeats)), C.byref(r))
+        return {"resolve_ms": float(r.value)}
 
     # -- kernel-level --------------------------------------------------------------------
     def trace_nearest(self, rays):

@@ -329,6 +329,15 @@ struct ReprojectState {
   bool rp_captured = false;       // a capture has been made since the last restart
   bool rp_from_reset = false;     // do_reset is being reached through crh_reset
   DevBuf<float4> d_rp_out[2];
+  // per-object history deltas (crh_set_reproject_motion): X_hist = the transforms in force when the history was captured; the table derived from (X_hist, c->xf),
+  // rebuilt whenever either changes and uploaded, stream-ordered on the context's stream, only while a record is flagged.  Never switched on: nothing allocated.
+  bool rpm_on = false; crh_reproject_motion_params rpm_par{};
+  std::vector<float> rpm_xf_hist; std::vector<crh_reproject_delta> rpm_table; uint32_t rpm_flagged = 0;
+  DevBuf<void> d_rpm_table;
+  bool rp_keep_restart = false;   // do_reset is being reached through a crh_set_transforms that keeps the history
+  bool rpm_staged = false;        // CRH_REPROJECT_STAGED=1: the LDS-staged form of the motion kernel while at most 64 records have flag 1 (measured, not the default: DESIGN.md section 6.12)
+  uint32_t rpm_n_staged = 0; bool rpm_stageable = false;      // flag-1 records uploaded in slot order behind the table; whether they are at most 64
+  uint64_t rp_launches[2] = {0, 0};      // k_reproject_resolve / k_reproject_resolve_motion launched by read-outs and captures (crh_get_reproject_launches)
 };
 
 // ---- viewport read-out (crh_view.cpp): the full RGB8 frame a view is resampled FROM, one scratch image per SET as the denoise filter has them -- set 0 the context's
@@ -526,11 +535,17 @@ inline void shading_changed(crh_ctx* c) { ++c->shade_gen; }      // crh_set_mate
 // BEFORE denoise_src, after the metering, which keeps reading `src`.
 int reproject_src(crh_ctx* c, hipStream_t on, const float4* src, int set, const float4** shown);
 int reproject_capture(crh_ctx* c, const crh_camera* next);      // crh_set_camera, BEFORE `next` replaces the camera in force: the header's LIFE CYCLE
-// do_reset: a restart reached through crh_reset keeps a fresh history, any other drops it; either way a new capture may follow
+// crh_set_transforms on a built scene, BEFORE `xf` replaces the transforms in force (per-object history deltas, LIFE CYCLE): the capture, and rp_keep_restart for the
+// restart that follows; nothing at all unless both features are on.  reproject_transforms_set: behind apply_objects, whatever it returned -- the table of the new
+// transforms, and the mark cleared.
+int reproject_transforms_begin(crh_ctx* c, const float* xf);
+int reproject_transforms_set(crh_ctx* c);
+// do_reset: a restart reached through crh_reset keeps a fresh history, one reached through such a crh_set_transforms a valid one, any other drops it; either way a
+// new capture may follow
 inline void reproject_restart(crh_ctx* c)
 {
-  const bool keep = c->rp_from_reset && c->rp_fresh;
-  c->rp_from_reset = c->rp_fresh = c->rp_captured = false;
+  const bool keep = (c->rp_from_reset && c->rp_fresh) || c->rp_keep_restart;
+  c->rp_from_reset = c->rp_fresh = c->rp_captured = c->rp_keep_restart = false;
   if (!keep) c->rp_valid = false;
 }
 inline void reproject_drop(crh_ctx* c) { c->rp_valid = c->rp_fresh = false; }      // the setters that change the picture without a restart of their own

@@ -382,8 +382,13 @@ int crh_set_transforms(crh_ctx* c, const float* xf, uint32_t nO)
   if (!all_finite(xf, 12 * (size_t)nO, 1.0e30f)) return fail(c, CRH_E_INVALID, "transform holds a NaN / Inf");
   CRH_HIP(hipSetDevice(c->device));
   if (!c->built) { c->xf.assign(xf, xf + 12 * (size_t)nO); return do_reset(c); }
-  // The manipulator calls this every frame (ImRaytraceControls.cxx:58-89).
-  return apply_objects(c, xf, nullptr);
+  // The manipulator calls this every frame (ImRaytraceControls.cxx:58-89).  With the per-object history deltas on (crh_reproject.cpp) the ending placement is
+  // captured first -- its guide comes from an id pass over the scene AS IT IS, and ensure_guide has finished before apply_objects patches or grows a record -- and
+  // the restart at the end of apply_objects keeps the history; do_reset invalidates the id buffer, so the new placement's guide is traced behind the uploads.
+  if (int rc = reproject_transforms_begin(c, xf)) return rc;
+  const int rc = apply_objects(c, xf, nullptr);
+  const int rc2 = reproject_transforms_set(c);           // (clears the mark whatever apply_objects returned)
+  return rc ? rc : rc2;
 }
 
 int crh_set_visibility(crh_ctx* c, const uint8_t* visible, uint32_t nO)

@@ -20,6 +20,27 @@ namespace crh {
 // crh_reproject_params as the kernel takes it: until = (float)until_samples (2^20 is exact)
 struct ReprojectRule { float max_history, until, normal_cos, depth_ratio; };
 
+// A record of THE DELTA TABLE (crh_reproject_delta) as the rule reads it: the rows of D as three float4 {D[4k], D[4k+1], D[4k+2], D[4k+3]}
+// On the DEVICE pad[0] of a flag-1 record is its slot among the flag-1 records (the staged form's index into LDS); the host twin's table has zero pads.
+struct ReprojectDelta { float4 r0, r1, r2; uint32_t flag, pad[3]; };
+static_assert(sizeof(ReprojectDelta) == 64 && sizeof(crh_reproject_delta) == 64, "a delta record is 64 bytes");
+
+// The table in force and the two caps; capped = a record has a non-zero flag.  lookup: the flag of `object` (0 outside the table) and, for flag 1 only, D.  On the
+// device the 4-byte flag is read per lane, the 48 bytes of D only by the lanes whose flag is 1, and a wavefront whose ballot shows no such lane skips the fetch as a whole.
+struct ReprojectMotion {
+  const ReprojectDelta* table = nullptr; uint32_t n_objects = 0; float max_moved = 0.f, max_static = 0.f; int capped = 0;
+  CRH_HD uint32_t lookup(int32_t object, float4& r0, float4& r1, float4& r2) const
+  {
+    uint32_t flag = 0u;
+    if ((uint32_t)object < n_objects) flag = table[object].flag;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__ballot(flag == 1u) == 0ull) return flag;
+#endif
+    if (flag == 1u) { const ReprojectDelta& r = table[object]; r0 = r.r0; r1 = r.r1; r2 = r.r2; }
+    return flag;
+  }
+};
+
 // A tap of the history against pixel p of the current view: the same object, a hit, and either the same triangle or two triangles whose planes meet at less than
 // the threshold angle with no step between the distance the old view EXPECTED of p's point (te) and the one it saw (q.t).
 CRH_HD bool reproject_match(const DenoisePx& p, const DenoisePx& q, float te, float normal_cos, float depth_ratio)
@@ -38,9 +59,11 @@ CRH_HD bool reproject_match(const DenoisePx& p, const DenoisePx& q, float te, fl
 // THE PIXEL RULE for pixel (x, y) of the current view: the float4 the denoise filter / the tone map receives.  C hands out the current view's image and guide, Hs the
 // history's image (its .w the effective sample count) and guide -- DenoisePlanesDevice on the device, DenoisePlanesHost in the host twin; (o, d) is the pixel-centre
 // ray; F the history's camera frame.  have_history false: every pixel passes through.  Every step is the header's, in its order.
-template <class PlanesC, class PlanesH>
-CRH_HD float4 reproject_pixel(const PlanesC& C, const PlanesH& Hs, bool have_history, uint32_t x, uint32_t y, uint32_t W, uint32_t H, const crh_v3& o, const crh_v3& d,
-                              const crh_reproject_frame& F, const ReprojectRule& R)
+// Motion false: the rule of "reprojected display history", and M is never looked at; true: that of "per-object history deltas" with the table M describes.
+// MotionT: where the table's records come from -- ReprojectMotion (memory) or the LDS-staged form of reproject_kernels.hip; the arithmetic is the same.
+template <bool Motion, class PlanesC, class PlanesH, class MotionT>
+CRH_HD float4 reproject_pixel_rule(const PlanesC& C, const PlanesH& Hs, bool have_history, uint32_t x, uint32_t y, uint32_t W, uint32_t H, const crh_v3& o, const crh_v3& d,
+                                   const crh_reproject_frame& F, const ReprojectRule& R, const MotionT& M)
 {
   const float4 a = C.colour(x, y);
   if (!have_history) return a;
@@ -48,7 +71,20 @@ CRH_HD float4 reproject_pixel(const PlanesC& C, const PlanesH& Hs, bool have_his
   if (p.triangle < 0 || !denoise_finite3(a) || a.w >= R.until) return a;
   // PROJECT
   const float tx = p.t * d.x, ty = p.t * d.y, tz = p.t * d.z;
-  const float Px = o.x + tx, Py = o.y + ty, Pz = o.z + tz;
+  float Px = o.x + tx, Py = o.y + ty, Pz = o.z + tz;
+  [[maybe_unused]] uint32_t flag = 0u;
+  if constexpr (Motion) {
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
+    flag = M.lookup(p.object, r0, r1, r2);
+    if (flag == 2u) return a;
+    if (flag == 1u) {
+      const float x0_ = r0.x * Px, x1_ = r0.y * Py, x2_ = r0.z * Pz;
+      const float y0_ = r1.x * Px, y1_ = r1.y * Py, y2_ = r1.z * Pz;
+      const float z0_ = r2.x * Px, z1_ = r2.y * Py, z2_ = r2.z * Pz;
+      const float nx_ = ((x0_ + x1_) + x2_) + r0.w, ny_ = ((y0_ + y1_) + y2_) + r1.w, nz_ = ((z0_ + z1_) + z2_) + r2.w;
+      Px = nx_; Py = ny_; Pz = nz_;
+    }
+  }
   const float qx = Px - F.eye[0], qy = Py - F.eye[1], qz = Pz - F.eye[2];
   const float xr0 = qx * F.right[0], xr1 = qy * F.right[1], xr2 = qz * F.right[2];
   const float yu0 = qx * F.up[0], yu1 = qy * F.up[1], yu2 = qz * F.up[2];
@@ -95,13 +131,23 @@ CRH_HD float4 reproject_pixel(const PlanesC& C, const PlanesH& Hs, bool have_his
   }
   if (!any) return a;
   const float hr = sr / S, hg = sg / S, hb = sb / S, hq = sn / S;
-  const float hn = hq < R.max_history ? hq : R.max_history;      // fminf
+  float hn = hq < R.max_history ? hq : R.max_history;      // fminf
+  if constexpr (Motion) {                                  // CAP
+    if (M.capped) { const float cap = flag == 1u ? M.max_moved : M.max_static; hn = hn < cap ? hn : cap; }
+  }
   // BLEND
   if (!(a.w > 0.f)) return make_float4(hr, hg, hb, hn);
   const float W2 = a.w + hn;
   const float ar = a.x * a.w, ag = a.y * a.w, ab = a.z * a.w;
   const float br = hr * hn, bg = hg * hn, bb = hb * hn;
   return make_float4((ar + br) / W2, (ag + bg) / W2, (ab + bb) / W2, W2);
+}
+
+template <class PlanesC, class PlanesH>
+CRH_HD float4 reproject_pixel(const PlanesC& C, const PlanesH& Hs, bool have_history, uint32_t x, uint32_t y, uint32_t W, uint32_t H, const crh_v3& o, const crh_v3& d,
+                              const crh_reproject_frame& F, const ReprojectRule& R)
+{
+  return reproject_pixel_rule<false>(C, Hs, have_history, x, y, W, H, o, d, F, R, ReprojectMotion{});
 }
 
 // What the resolve kernel reads of the history (all W * H records; never read when `valid` is 0) ...
@@ -111,11 +157,24 @@ struct ReprojectHistory { const float4* img; const float4* guide; const int2* id
 // current view and `out` hold S.width * S.height records; `out` aliases none of the inputs
 void launch_reproject_resolve(hipStream_t stream, const DScene& S, const float4* guide, const int2* ids, const float4* a, const ReprojectHistory& hist, const ReprojectRule& R,
                               float4* out);
+// ... with THE DELTA TABLE M describes (device memory, M.n_objects records): k_reproject_resolve_motion, the same pixel-to-lane mapping.  The callers launch it only
+// while a record is flagged (M.capped); without one, launch_reproject_resolve gives the same image with the plain kernel's time.
+void launch_reproject_resolve_motion(hipStream_t stream, const DScene& S, const float4* guide, const int2* ids, const float4* a, const ReprojectHistory& hist,
+                                     const ReprojectRule& R, const ReprojectMotion& M, float4* out);
+// THE STAGED FORM (CRH_REPROJECT_STAGED=1, at most kReprojectStagedMax flag-1 records): the n_staged flag-1 records, which the caller keeps in slot order BEHIND the
+// table's M.n_objects records, are copied into LDS by every workgroup; the lanes then read flag and slot from memory and D from LDS.  The same bytes.
+void launch_reproject_resolve_motion_staged(hipStream_t stream, const DScene& S, const float4* guide, const int2* ids, const float4* a, const ReprojectHistory& hist,
+                                            const ReprojectRule& R, const ReprojectMotion& M, uint32_t n_staged, float4* out);
 // the host twin: the same rule in a plain loop over host planes; rays: 8 floats per pixel {o.xyz, -, d.xyz, -}; hist_rgba == nullptr: no history
 void reproject_host(const float4* a, const float* rays, const int32_t* object, const int32_t* triangle, const float* t, const float4* hist_rgba, const int32_t* hist_object,
                     const int32_t* hist_triangle, const float* hist_t, const crh_reproject_frame& F, const OutlineTri* table, uint32_t n_tri, uint32_t W, uint32_t H,
                     const ReprojectRule& R, float4* out);
+// ... with the table (host memory; M.table == nullptr: reproject_host)
+void reproject_motion_host(const float4* a, const float* rays, const int32_t* object, const int32_t* triangle, const float* t, const float4* hist_rgba, const int32_t* hist_object,
+                           const int32_t* hist_triangle, const float* hist_t, const crh_reproject_frame& F, const OutlineTri* table, uint32_t n_tri, uint32_t W, uint32_t H,
+                           const ReprojectRule& R, const ReprojectMotion& M, float4* out);
 
+constexpr uint32_t kReprojectStagedMax = 64;
 constexpr int kReprojectBlock = 256;      // four wavefronts, each 64 consecutive pixels of one row
 
 }  // namespace crh

@@ -206,6 +206,16 @@ class View(Backend):
         """(H, W, 4) float32: the image the denoise filter / the tone map of an LDR read-out issued now would receive"""
         return self.read_reprojected()
 
+    def SetReprojectMotion(self, max_history_moved=16.0, max_history_static=8.0):
+        """keep the picture through an object drag as well: with SetReproject on, set_transforms from now on captures what the ending placement displayed and a moved
+        object's history follows it; the two caps bound the history's weight on the moved object's pixels and -- while any object is off its captured placement --
+        on all the others (their geometry is unchanged, their lighting is not).  Nothing restarts."""
+        self.set_reproject_motion(True, max_history_moved=float(max_history_moved), max_history_static=float(max_history_static))
+
+    def ClearReprojectMotion(self):
+        """set_transforms drops the history again, as in a view that never called SetReprojectMotion"""
+        self.set_reproject_motion(False)
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -644,6 +654,54 @@ def reproject_host(accum, rays, object_px, triangle_px, t_px, history, table, **
                                 out.ctypes.data_as(fp))
     if rc != 0:
         raise BackendError(f"crh_reproject_host -> {rc}")
+    return out
+
+
+def reproject_delta_host(xf_hist, xf_cur):
+    """crh_reproject_delta_host on the host only (no GPU): the delta table (abi.REPROJECT_DELTA_DTYPE records) of two (n, 12) float32 arrays of 3x4 transforms --
+    those in force when the history was captured, and those in force now"""
+    lib = load_library()
+    a, b = np.ascontiguousarray(xf_hist, np.float32).reshape(-1, 12), np.ascontiguousarray(xf_cur, np.float32).reshape(-1, 12)
+    assert a.shape == b.shape
+    out = np.zeros(len(a), abi.REPROJECT_DELTA_DTYPE)
+    fp = C.POINTER(C.c_float)
+    rc = lib.crh_reproject_delta_host(a.ctypes.data_as(fp), b.ctypes.data_as(fp), C.c_uint32(len(a)), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise BackendError(f"crh_reproject_delta_host -> {rc}")
+    return out
+
+
+def reproject_motion_host(accum, rays, object_px, triangle_px, t_px, history, table, delta_table, motion=None, **params):
+    """crh_reproject_motion_host on the host only (no GPU): reproject_host's arguments, the delta table as reproject_delta_host returns it (None: the image of
+    reproject_host) and motion = dict of crh_reproject_motion_params fields (None: the defaults); the (H, W, 4) float32 image read_reprojected returns"""
+    from .binding import reproject_motion_params, reproject_params
+    lib = load_library()
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    img = np.ascontiguousarray(accum, np.float32)
+    ob, tr, t = np.ascontiguousarray(object_px, np.int32), np.ascontiguousarray(triangle_px, np.int32), np.ascontiguousarray(t_px, np.float32)
+    assert ob.ndim == 2 and ob.shape == tr.shape == t.shape and img.shape == ob.shape + (4,)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    assert len(r) == ob.size
+    tb = np.zeros(0, abi.OUTLINE_TABLE_DTYPE) if table is None else np.ascontiguousarray(table, abi.OUTLINE_TABLE_DTYPE)
+    h = [None] * 5
+    if history is not None:
+        himg = np.ascontiguousarray(history["rgba"], np.float32)
+        hob, htr, ht = np.ascontiguousarray(history["ob"], np.int32), np.ascontiguousarray(history["tr"], np.int32), np.ascontiguousarray(history["t"], np.float32)
+        assert himg.shape == img.shape and hob.shape == htr.shape == ht.shape == ob.shape
+        f = history["frame"]
+        F = abi.crh_reproject_frame()
+        F.eye[:] = [float(x) for x in f["eye"]]; F.right[:] = [float(x) for x in f["right"]]; F.up[:] = [float(x) for x in f["up"]]; F.fwd[:] = [float(x) for x in f["fwd"]]
+        F.tan_half, F.aspect, F.ortho_scale, F.is_ortho = float(f["tan_half"]), float(f["aspect"]), float(f["ortho_scale"]), int(f["is_ortho"])
+        h = [himg.ctypes.data_as(fp), hob.ctypes.data_as(ip), htr.ctypes.data_as(ip), ht.ctypes.data_as(fp), C.byref(F)]
+    p = reproject_params(**params)
+    dt = None if delta_table is None else np.ascontiguousarray(delta_table, abi.REPROJECT_DELTA_DTYPE)
+    mp = reproject_motion_params(**(motion or {}))
+    out = np.zeros(img.shape, np.float32)
+    rc = lib.crh_reproject_motion_host(img.ctypes.data_as(fp), r.ctypes.data_as(fp), ob.ctypes.data_as(ip), tr.ctypes.data_as(ip), t.ctypes.data_as(fp), *h,
+                                       tb.ctypes.data_as(C.c_void_p) if len(tb) else None, C.c_uint32(len(tb)), C.c_uint32(ob.shape[1]), C.c_uint32(ob.shape[0]), C.byref(p),
+                                       None if dt is None else dt.ctypes.data_as(C.c_void_p), C.c_uint32(0 if dt is None else len(dt)), C.byref(mp), out.ctypes.data_as(fp))
+    if rc != 0:
+        raise BackendError(f"crh_reproject_motion_host -> {rc}")
     return out
 
 

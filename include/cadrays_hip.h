@@ -811,6 +811,89 @@ CRH_API int crh_reproject_host(const float* accum_rgba, const float* rays_px, co
                                const float* hist_rgba, const int32_t* hist_object, const int32_t* hist_triangle, const float* hist_t, const crh_reproject_frame* hist_cam,
                                const void* table, uint32_t n_tri, uint32_t width, uint32_t height, const crh_reproject_params* p, float* rgba_out /* width*height*4 */);
 
+/* --- reprojected display history, per-object history deltas (crh_reproject.cpp; k_reproject_resolve_motion in reproject_kernels.hip) ----------------
+ * The manipulator drag (ImRaytraceControls.cxx:58-89) calls SetLocation -- crh_set_transforms -- on every GUI frame, and a restart reached that way drops the
+ * history above: every frame of the drag is a raw 1-spp image, the parts that did not move included.  With this feature on AS WELL, crh_set_transforms captures
+ * like crh_set_camera and keeps the history, and the rule carries a point on a moved object from the transform the object has NOW to the one it had WHEN THE
+ * HISTORY WAS TAKEN before it projects it into the history's camera frame.  The guide's normals are object-space and the ids carry the object, so match() needs
+ * no change.  Opt-in; no effect while crh_set_reproject is off.  Off or never set: nothing is allocated, nothing is launched, crh_set_transforms drops the
+ * history, and every byte is that of a context that never heard of it.  On with no transform changed since the history was taken: the kernel, and so the
+ * bytes and the time, of the section above.  The reference has NO counterpart: OCCT's path tracer shows the raw accumulation.
+ *   THE DELTA TABLE, one 64-byte record per object k: X_hist[k] = the object's 3x4 transform (row-major, absolute, as crh_set_transforms takes it) when the
+ *   history was captured, X_cur[k] = the one in force.
+ *     flag 0  the twelve floats of X_hist[k] and X_cur[k] are bitwise equal.  D is all zero and never read: such a pixel runs the arithmetic of the section above.
+ *     flag 1  D = X_hist[k] o X_cur[k]^-1, computed in DOUBLE from the float32 inputs, every product and every sum rounded (to double), NO fused multiply-add, in
+ *             this order.  With M = X_cur[k], rows r0 = (M[0], M[1], M[2]), r1 = (M[4], M[5], M[6]), r2 = (M[8], M[9], M[10]), t = (M[3], M[7], M[11]):
+ *               cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), each component two products and one difference;
+ *               dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ *               c0 = cross(r1, r2), c1 = cross(r2, r0), c2 = cross(r0, r1); det = dot(r0, c0);
+ *               the inverse's rows, each entry a DIVISION by det (no reciprocal): i0 = (c0.x, c1.x, c2.x) / det, i1 = (c0.y, c1.y, c2.y) / det,
+ *               i2 = (c0.z, c1.z, c2.z) / det; its translation u.j = -dot(i_j, t);
+ *               with A = X_hist[k], row j of A = (A[4j], A[4j+1], A[4j+2]), translation A[4j+3]:
+ *               D[4j+m] = (A[4j] i0.m + A[4j+1] i1.m) + A[4j+2] i2.m for m = 0, 1, 2;  D[4j+3] = ((A[4j] u.0 + A[4j+1] u.1) + A[4j+2] u.2) + A[4j+3];
+ *             then each of the twelve results is rounded ONCE to float32.
+ *     flag 2  no history for this object: det is zero or not finite, or an entry of D is not finite after the rounding to float32.  D is all zero.
+ *   The pad words are zero.  A numpy float64 restatement of these lines gives the same bytes (tests/reproject_motion_reference.py).
+ *   THE RULE is the one above with two changes; object[p] = g1.object[p], flag(p) = the flag of record object[p], 0 when object[p] lies outside 0 .. n_objects - 1.
+ *   PROJECT       P = o + t d as above.  flag(p) == 2: no history (pass-through).  flag(p) == 1: with D of record object[p],
+ *                 P'.k = ((D[4k] P.x + D[4k+1] P.y) + D[4k+2] P.z) + D[4k+3], plain float32, every operation rounded, no fused multiply-add, and P' takes the place
+ *                 of P: q = P' - eye0, te, the taps and match() unchanged.  flag(p) == 0: unchanged.
+ *   CAP           after hn = fminf(sn / S, max_history), and only while at least one record of the table has a non-zero flag:
+ *                 flag(p) == 1: hn = fminf(hn, max_history_moved); flag(p) == 0: hn = fminf(hn, max_history_static).  A static pixel's geometry is unchanged but
+ *                 its lighting is not -- the moved part's shadow and reflection lag in the history -- so the host has a knob.  No record flagged: no cap.
+ *   LIFE CYCLE    While on (and crh_set_reproject on), the context remembers X_hist: every capture, by either setter, copies the transforms in force at that
+ *                 moment; switching the feature on while a history is valid takes the transforms in force (with the feature off every transform change had
+ *                 dropped the history).  The table is derived from (X_hist, X_cur) whenever either changes; read-outs, crh_read_reprojected and captures resolve
+ *                 with the table in force.  crh_set_transforms on a built scene CAPTURES, before the new transforms replace the old ones, when all of: both
+ *                 features are on; the new transforms differ bitwise from those in force; no capture has been made since the last restart;
+ *                 crh_spec.raygen_bilinear == 0; frames_done > 0 (with frames_done == 0 it does not capture and keeps a valid history as it is: the table is
+ *                 always derived from the transforms in force, so a skipped capture is geometrically correct); an accumulator of this size exists.  The restart
+ *                 inside crh_set_transforms then KEEPS a valid history.  Everything else that drops the history above still drops it: crh_set_visibility,
+ *                 crh_add_object, geometry, crh_build, materials, lights, environment, textures, crh_set_params, crh_set_spec, crh_load_accum, a change of the
+ *                 frame size, crh_set_reproject(NULL).  crh_set_reproject_motion(NULL) drops it only when a record is flagged.  Manipulator sequence
+ *                 (INTEGRATION.md): crh_set_transforms, Redraw, read-out -- no crh_reset.
+ *   KNOWN LIMITS: the moved part's shadow, reflection and bounce light lag in the history of the static pixels by up to max_history_static samples. */
+typedef struct crh_reproject_motion_params {
+  float max_history_moved;   /* 1..1024, finite: cap of the history's count on pixels of a moved object (flag 1); default 16 = max_history's default */
+  float max_history_static;  /* 1..1024, finite: ... on the other pixels while any object is flagged; default 8                                       */
+} crh_reproject_motion_params;   /* 8 B */
+typedef struct crh_reproject_delta {
+  float    D[12];            /* row-major 3x4; all zero unless flag == 1 */
+  uint32_t flag;             /* 0 unchanged, 1 moved, 2 no history       */
+  uint32_t pad[3];           /* zero                                      */
+} crh_reproject_delta;           /* 64 B */
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  16, 8 */
+CRH_API void crh_reproject_motion_defaults(crh_reproject_motion_params* p);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  Switch the per-object deltas on with these caps, or off with NULL -- the state
+ * of a new context.  Display state, crh_set_reproject's contract: no restart, no work on any stream, allowed before crh_build.  CRH_E_INVALID with a message: a cap
+ * outside 1..1024, a NaN or Inf.  Changing the caps keeps the history; NULL drops it only when a record of the table in force is flagged. */
+CRH_API int crh_set_reproject_motion(crh_ctx* ctx, const crh_reproject_motion_params* p /* NULL = off */);
+/* (no counterpart in the reference: OCCT's path tracer shows the raw accumulation)  The caps in force (the defaults while off), whether the feature is on, and the
+ * number of records with a non-zero flag in the table a read-out issued now would use (0 while off or without a valid history); every pointer may be NULL. */
+CRH_API int crh_get_reproject_motion(crh_ctx* ctx, crh_reproject_motion_params* out, int* on, uint32_t* n_flagged);
+/* Debug counters (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): how often the read-outs, crh_read_reprojected and the captures
+ * of this context have launched k_reproject_resolve (*plain) and k_reproject_resolve_motion (*motion) since it was created -- the second only ever while a record
+ * of the table in force is flagged.  The micro-benchmarks are not counted.  Either pointer may be NULL. */
+CRH_API int crh_get_reproject_launches(crh_ctx* ctx, uint64_t* plain, uint64_t* motion);
+/* Micro-benchmark (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): device time of k_reproject_resolve_motion with the table in
+ * force, `repeats` times between two HIP events on the context's stream, in milliseconds per launch.  When no record is flagged (or the feature is off) a stand-in
+ * table flags EVERY object with its exact identity delta -- the worst case for fetches, the same image -- and without a valid history the current view stands in
+ * as in crh_bench_reproject.  Synchronous; changes nothing a read-out could see.  Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_bench_reproject_motion(crh_ctx* ctx, uint32_t repeats, float* resolve_ms);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): THE DELTA TABLE above from two arrays of
+ * n_objects transforms, 64 * n_objects bytes into table_out (which need not be aligned).  NULL anywhere with n_objects > 0: CRH_E_INVALID; n_objects == 0 writes
+ * nothing.  Inputs that are not finite simply give flag 2 (or flag 0 when the two transforms are bitwise equal). */
+CRH_API int crh_reproject_delta_host(const float* xf_hist /* 12*n */, const float* xf_cur /* 12*n */, uint32_t n_objects, void* table_out /* 64*n */);
+/* Host-only, no device and no context (no counterpart in the reference: OCCT's path tracer shows the raw accumulation): crh_reproject_host with THE RULE of this
+ * section -- the same function k_reproject_resolve_motion compiles.  delta_table as crh_reproject_delta_host returns it (need not be aligned); NULL with
+ * n_objects == 0: the image of crh_reproject_host, bitwise, and mp is not read.  The refusals of crh_reproject_host, and CRH_E_INVALID for n_objects > 0 without a
+ * table, a table without mp, a cap outside 1..1024 or not finite, a flag above 2. */
+CRH_API int crh_reproject_motion_host(const float* accum_rgba, const float* rays_px, const int32_t* object_px, const int32_t* triangle_px, const float* t_px,
+                                      const float* hist_rgba, const int32_t* hist_object, const int32_t* hist_triangle, const float* hist_t,
+                                      const crh_reproject_frame* hist_cam, const void* table, uint32_t n_tri, uint32_t width, uint32_t height,
+                                      const crh_reproject_params* p, const void* delta_table, uint32_t n_objects, const crh_reproject_motion_params* mp,
+                                      float* rgba_out /* width*height*4 */);
+
 /* --- viewport read-out (crh_view.cpp, cadrays_amd/csrc/view_kernels.hip) ------------------------------------------------------------------------
  * The application renders into a target whose size the user sets apart from the window's ("Resolution" panel, SettingsWidget.cxx:104-149, 128 .. 2048 px per
  * side), letterboxes it into the panel (AppViewer.cxx:929-957) and draws the FBO's GL_RGB8 colour texture at the panel's size (AppViewer.cxx:1095-1102): the GL

@@ -1,5 +1,5 @@
 // sanitize_reproject_host.cpp -- the host-only side of the reprojected display history (crh_reproject_host, crh_reproject_frame_host; cadrays_amd/csrc/crh_reproject.cpp,
-// reproject_kernels.h: the projection, the gather, the blend) under AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, no device, no context,
+// reproject_kernels.h: the projection, the gather, the blend; and the per-object history deltas: crh_reproject_delta_host, crh_reproject_motion_host) under AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, no device, no context,
 // nothing loaded into an interpreter.
 // Build and run:  make -C cadrays_amd/csrc sanitize-reproject   (links the library's own translation units, host code compiled with -fsanitize=address,undefined)
 #include <cmath>
@@ -90,6 +90,60 @@ int main()
         for (size_t i = 0; i < n; ++i)
           if ((tr[i] < 0 || rgba[4 * i + 3] >= (float)p.until_samples) && std::memcmp(&out[4 * i], &rgba[4 * i], 16) != 0) { std::printf("a pixel that should pass through did not\n"); ++failures; break; }
       }
+    // per-object history deltas: the table of crh_reproject_delta_host (exactly-sized blocks, an unaligned copy) through crh_reproject_motion_host; the objects
+    // of `fill` are 0 .. 2, so a table of two records leaves object 2 outside it; an unflagged table and no table give crh_reproject_host's bytes
+    {
+      const float xh[36] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+      const float xc[36] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0.9f, -0.2f, 0, 0.3f, 0.2f, 0.9f, 0, -0.1f, 0, 0, 1.1f, 0.05f, 0, 0, 0, 1, 0, 0, 0, 2, 0, 0, 0, 3};
+      std::vector<crh_reproject_delta> dt(3), zero(3);
+      std::vector<unsigned char> dt_off(sizeof(crh_reproject_delta) * 3 + 1);
+      failures += crh_reproject_delta_host(xh, xc, 3, dt.data()) != CRH_OK || crh_reproject_delta_host(xh, xc, 3, dt_off.data() + 1) != CRH_OK;
+      failures += std::memcmp(dt.data(), dt_off.data() + 1, sizeof(crh_reproject_delta) * 3) != 0;
+      failures += dt[0].flag != 0u || dt[1].flag != 1u || dt[2].flag != 2u;
+      failures += crh_reproject_delta_host(xh, xh, 3, zero.data()) != CRH_OK || zero[0].flag || zero[1].flag || zero[2].flag;
+      const crh_reproject_motion_params mps[] = {{16.f, 8.f}, {1.f, 1024.f}, {1024.f, 1.f}, {2.5f, 1.5f}};
+      std::vector<float> plain(4 * n), moved(4 * n);
+      for (const crh_reproject_frame& F : frames) {
+        failures += crh_reproject_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &F, table.data(), nT, W, H, &def, plain.data()) != CRH_OK;
+        for (const crh_reproject_motion_params& mp : mps) {
+          for (uint32_t nO = 1; nO <= 3; ++nO) {
+            int rc = crh_reproject_motion_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &F, table.data(), nT, W, H, &def,
+                                               dt.data(), nO, &mp, out.data());
+            if (rc != CRH_OK) { std::printf("reproject motion %ux%u -> %d\n", W, H, rc); ++failures; continue; }
+            rc = crh_reproject_motion_host(rgba_off.data() + 1, rays.data(), ob.data(), tr.data(), t.data(), hist_off.data() + 1, hob.data(), htr.data(), ht.data(), &F, raw.data() + 1, nT, W, H,
+                                           &def, dt_off.data() + 1, nO, &mp, out_unaligned.data());
+            failures += rc != CRH_OK || std::memcmp(out.data(), out_unaligned.data(), 16 * n) != 0;
+            if (nO == 3)
+              for (size_t i = 0; i < n; ++i)
+                if ((tr[i] < 0 || ob[i] == 2) && std::memcmp(&out[4 * i], &rgba[4 * i], 16) != 0) { std::printf("a pixel of an object without history did not pass through\n"); ++failures; break; }
+          }
+          failures += crh_reproject_motion_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &F, table.data(), nT, W, H, &def,
+                                                zero.data(), 3, &mp, moved.data()) != CRH_OK || std::memcmp(moved.data(), plain.data(), 16 * n) != 0;
+        }
+        failures += crh_reproject_motion_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &F, table.data(), nT, W, H, &def,
+                                              nullptr, 0, nullptr, moved.data()) != CRH_OK || std::memcmp(moved.data(), plain.data(), 16 * n) != 0;
+      }
+      // the refusals of the new entry points
+      const crh_reproject_motion_params good = mps[0], bad_lo = {0.5f, 8.f}, bad_hi = {16.f, 1025.f}, bad_nan = {nan, 8.f}, bad_inf = {16.f, inf};
+      auto call = [&](const void* d, uint32_t nO, const crh_reproject_motion_params* mp) {
+        return crh_reproject_motion_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &frames[0], table.data(), nT, W, H, &def, d, nO, mp, out.data());
+      };
+      failures += call(dt.data(), 3, &good) != CRH_OK;
+      failures += call(nullptr, 3, &good) != CRH_E_INVALID || call(dt.data(), 3, nullptr) != CRH_E_INVALID;
+      failures += call(dt.data(), 3, &bad_lo) != CRH_E_INVALID || call(dt.data(), 3, &bad_hi) != CRH_E_INVALID || call(dt.data(), 3, &bad_nan) != CRH_E_INVALID || call(dt.data(), 3, &bad_inf) != CRH_E_INVALID;
+      std::vector<crh_reproject_delta> three = dt; three[1].flag = 3u;
+      failures += call(three.data(), 3, &good) != CRH_E_INVALID;
+      failures += crh_reproject_delta_host(nullptr, xc, 3, dt.data()) != CRH_E_INVALID || crh_reproject_delta_host(xh, nullptr, 3, dt.data()) != CRH_E_INVALID;
+      failures += crh_reproject_delta_host(xh, xc, 3, nullptr) != CRH_E_INVALID || crh_reproject_delta_host(nullptr, nullptr, 0, nullptr) != CRH_OK;
+      const float odd[24] = {nan, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1e30f, 0, 0, 0, 0, 1e30f, 0, 0, 0, 0, 1e30f, inf};
+      const float tiny[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1e-30f, 0, 0, 0, 0, 1e-30f, 0, 0, 0, 0, 1e-30f, 0};
+      crh_reproject_delta two[2];
+      failures += crh_reproject_delta_host(odd, tiny, 2, two) != CRH_OK || two[0].flag != 2u || two[1].flag != 2u;
+      failures += crh_reproject_delta_host(tiny, odd, 2, two) != CRH_OK || two[0].flag != 2u || two[1].flag != 2u;
+      crh_reproject_motion_params got; crh_reproject_motion_defaults(&got); crh_reproject_motion_defaults(nullptr);
+      failures += !(got.max_history_moved == 16.f) || crh_set_reproject_motion(nullptr, &got) != CRH_E_INVALID || crh_get_reproject_motion(nullptr, &got, nullptr, nullptr) != CRH_E_INVALID;
+      failures += crh_bench_reproject_motion(nullptr, 1, nullptr) != CRH_E_INVALID;
+    }
     // no table at all, and no history at all: the accumulator, bitwise
     failures += crh_reproject_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), hist.data(), hob.data(), htr.data(), ht.data(), &frames[0], nullptr, 0, W, H, &def, out.data()) != CRH_OK;
     failures += crh_reproject_host(rgba.data(), rays.data(), ob.data(), tr.data(), t.data(), nullptr, nullptr, nullptr, nullptr, nullptr, table.data(), nT, W, H, &def, out.data()) != CRH_OK;
