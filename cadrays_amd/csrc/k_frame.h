@@ -5,7 +5,7 @@
 // wavefronts while the rest of the chip idles; a 512-sample batch hides that (25 ms per launch), a lone 1080p frame of 2 M paths is twenty such drains: 4.3 ms
 // for 1.2 ms of work at the batch rate, and the application restarts with a lone frame on every camera move (AppViewer.cxx:979-984).
 // What.  Every workgroup -- ONE of 16 wavefronts per compute unit -- is a small streaming path tracer over its own paths: it claims path slots in chunks from ONE
-// global cursor, generates their camera rays, and keeps two rings in LDS -- rays to trace (nearest-hit and shadow rays mixed) and hit records to shade.  Thirteen
+// global cursor, generates their camera rays, and keeps three rings in LDS -- rays to trace (nearest-hit and shadow rays mixed) and hit records to shade (surface hits and misses apart).  Thirteen
 // wavefronts trace with the persistent engine of k_traversal.h (lanes refill from the ring as rays finish; when the ring is dry the idle lanes take over parts of
 // the long rays' stacks, DON); the last three only shade (survivors and shadow rays go back into the ray ring) and claim the next chunk when the ray ring runs low.
 // No stage ever waits for another workgroup, and a path's bounces follow each other without a launch boundary: the only drain is the end of the frame.
@@ -28,9 +28,6 @@ constexpr int      kFrameMats  = 32;            // materials staged in LDS (4 KB
 #endif
 constexpr int      kFrameBlock = CRH_FRAME_BLOCK;
 constexpr uint32_t frame_pow2(uint32_t x) { uint32_t p = 1; while (p < x) p <<= 1; return p; }
-#ifndef CRH_FRAME_MISS_RING
-#define CRH_FRAME_MISS_RING 1                   // round 6 experiment: rays that hit nothing wait in a ring of their own, so that a shading batch is either all misses (environment /
-#endif                                          // implicit light, the path ends: a few hundred instructions) or all surface hits (the BSDF code) -- profiles/r6/lone_frame.md
 #ifndef CRH_FRAME_RING_MUL
 #define CRH_FRAME_RING_MUL 4
 #endif
@@ -120,18 +117,15 @@ __global__ __launch_bounds__(kFrameBlock, CRH_FRAME_MINWAVES) void k_frame(DScen
   __shared__ uint32_t stk[kLdsStack * kBlock];
   __shared__ uint32_t s_bound[CRH_FRAME_DON ? kBlock : 1];
   __shared__ float4 s_mats[kFrameMats * 8];
-  __shared__ uint32_t s_rq[kFrameRing], s_sq[kFrameRing];
-#if CRH_FRAME_MISS_RING
-  __shared__ uint32_t s_mq[kFrameRing];      // hit records that are misses
-#endif
+  // Rays that hit nothing wait in a ring of their own, so that a shading batch is either all misses (environment / implicit light, the path ends: a few hundred
+  // instructions) or all surface hits (the BSDF code) -- profiles/r6/lone_frame.md
+  __shared__ uint32_t s_rq[kFrameRing], s_sq[kFrameRing], s_mq[kFrameRing];      // rays to trace, surface hits to shade, misses to shade
   __shared__ uint32_t s_ctl[12];     // [0] ray head, [1] ray tail, [2] shade head, [3] shade tail, [4] live paths, [5] the slot cursor has run out, [6] error, [8] miss head, [9] miss tail
   uint32_t* const rq_head = &s_ctl[0]; uint32_t* const rq_tail = &s_ctl[1]; uint32_t* const sq_head = &s_ctl[2]; uint32_t* const sq_tail = &s_ctl[3];
   uint32_t* const live = &s_ctl[4]; uint32_t* const cursor_out = &s_ctl[5]; uint32_t* const wg_err = &s_ctl[6];      // [6]: a spin loop of this workgroup gave up
   for (uint32_t i = threadIdx.x; i < kFrameRing; i += (uint32_t)kBlock) { s_rq[i] = kFrameEmpty; s_sq[i] = kFrameEmpty; }
-#if CRH_FRAME_MISS_RING
   for (uint32_t i = threadIdx.x; i < kFrameRing; i += (uint32_t)kBlock) s_mq[i] = kFrameEmpty;
   uint32_t* const mq_head = &s_ctl[8]; uint32_t* const mq_tail = &s_ctl[9];
-#endif
   if (threadIdx.x < 12u) s_ctl[threadIdx.x] = 0u;
   const bool mats_in_lds = S.n_mats <= (uint32_t)kFrameMats;
   if (mats_in_lds) for (uint32_t i = threadIdx.x; i < S.n_mats * 8u; i += (uint32_t)kBlock) s_mats[i] = S.mats[i];
@@ -157,13 +151,8 @@ __global__ __launch_bounds__(kFrameBlock, CRH_FRAME_MINWAVES) void k_frame(DScen
 
   auto shade_some = [&](bool misses) {
     uint32_t base = 0;
-#if CRH_FRAME_MISS_RING
     uint32_t* const q_slots = misses ? s_mq : s_sq;
     const uint32_t n = ring_claim(misses ? mq_head : sq_head, misses ? mq_tail : sq_tail, 64u, base);
-#else
-    uint32_t* const q_slots = s_sq; (void)misses;
-    const uint32_t n = ring_claim(sq_head, sq_tail, 64u, base);
-#endif
     if (n == 0u) return;
     const bool mine = lane < n;
 #if CRH_FRAME_STATS
@@ -279,13 +268,9 @@ __global__ __launch_bounds__(kFrameBlock, CRH_FRAME_MINWAVES) void k_frame(DScen
         if (to_shade) P.hit[tag] = h;
         if (__ballot(to_shade) != 0ull) {
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-#if CRH_FRAME_MISS_RING
           const bool miss = __float_as_int(h.w) < 0;
           ring_push(s_sq, sq_tail, to_shade && !miss, tag, wg_err);
           ring_push(s_mq, mq_tail, to_shade && miss, tag, wg_err);
-#else
-          ring_push(s_sq, sq_tail, to_shade, tag, wg_err);
-#endif
         }
         wave_sub(live, fin && any_l && !go_on);                      // a shadow ray with nothing behind it: the path is done
         return go_on;
@@ -307,15 +292,10 @@ __global__ __launch_bounds__(kFrameBlock, CRH_FRAME_MINWAVES) void k_frame(DScen
   uint32_t idle_spins = 0;
   for (;;) {
     const uint32_t nr = ring_count(rq_head, rq_tail);
-#if CRH_FRAME_MISS_RING
     const uint32_t nh = ring_count(sq_head, sq_tail), nm = ring_count(mq_head, mq_tail), ns = nh + nm;
     // which ring a shading batch comes from: a full batch of surface hits first (they refill the ray ring), then a full batch of misses, else the fuller one
     const bool from_misses = nh >= 64u ? false : (nm >= 64u ? true : nm > nh);
     const bool full_batch = nh >= 64u || nm >= 64u;
-#else
-    const uint32_t ns = ring_count(sq_head, sq_tail);
-    const bool from_misses = false, full_batch = ns >= 64u;
-#endif
     // one call site per stage (each is a few thousand instructions, inlined): decide first, then act
     int act = 0;                                                     // 0 idle, 1 shade, 2 generate, 3 trace
     if (feeder) {

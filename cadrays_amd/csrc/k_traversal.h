@@ -15,16 +15,6 @@
 #ifndef CRH_POOL_DIV
 #define CRH_POOL_DIV 2
 #endif
-#ifndef CRH_POSTPONE_LEAF
-#define CRH_POSTPONE_LEAF 0    // round 6 experiment: 1 = the frame kernel's engine keeps descending with ONE triangle leaf postponed per lane (speculative while-while:
-#endif                         // a lane that reaches a leaf does not drop out of the inner steps of its wavefront), 2 = every non-counting single-level engine
-#ifndef CRH_HUNT_NOOP_CALLS
-#define CRH_HUNT_NOOP_CALLS 0  // 1 re-creates the build of round 6 in which k_trace_rays<ANY, COUNT, TWO> answered wrong: calls of a lambda whose body is `if (false && ..)`
-#endif                         // around the inner steps -- nothing at source level -- and hipcc 7.2's si-form-memory-clauses pass miscompiles that instantiation (DESIGN.md section 7,
-                               // profiles/r6/hunt_anyhit_found.md, tests/hunts/anyhit_split_min.py).  The default source has no such call.
-#ifndef CRH_FRAME_PARK
-#define CRH_FRAME_PARK 0       // round 6 experiment: the frame engine runs its triangle step only when at least this many lanes hold a leaf, or none can descend (0: every turn)
-#endif
 #ifndef CRH_REFILL_IDLE
 #define CRH_REFILL_IDLE 12     // refill a wavefront once this many of its 64 lanes have no ray
 #endif
@@ -36,9 +26,6 @@
 #endif
 #if CRH_FRAME_STATS || CRH_FRAME_TIMELINE
 __device__ unsigned long long g_frame_stats[32];      // tools/frame_stats.py names the entries
-#endif
-#ifndef CRH_EXP_EARLY_TRI
-#define CRH_EXP_EARLY_TRI 0     // hunt scaffold only (tests/hunts/two_level_anyhit_counting.py)
 #endif
 #ifndef CRH_POOL_CHUNK
 #define CRH_POOL_CHUNK 256     // measured: 64 -> 2257, 128 -> 2305, 256 -> 2308, 512 -> 2266, 1024 -> 2136 Mrays/s (big pools starve late bounces)
@@ -71,9 +58,13 @@ __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c)
 // A wavefront owns 64 ray slots.  It takes rays from a wave-local pool (kPoolChunk queue entries claimed with
 // one atomic on the global cursor) and REFILLS idle lanes as soon as CRH_REFILL_IDLE of them have finished,
 // instead of waiting for the slowest ray of a 64-ray packet.  Inside, the classic "while-while" shape keeps
-// lanes convergent: (A) every lane descends inner nodes until it holds a leaf (or runs dry), (B) all lanes
-// holding a leaf test its triangles together.  The per-ray sequence of node visits and triangle tests -- and
-// therefore every result bit and counter -- is exactly the ordered stack traversal of DESIGN.md section 3.
+// lanes convergent: (A) every lane descends inner nodes until it holds a leaf (at most CRH_INNER_STEPS steps per turn),
+// (B) all lanes holding a leaf test its triangle together (or enter the object of an instance leaf).  The per-ray sequence of
+// node visits and triangle tests -- and therefore every result bit and counter -- is exactly the ordered stack traversal of
+// DESIGN.md section 3.
+//   One turn of the engine's loop: refill idle lanes (ray start-up: CRH_START_RAY) -- donate (DON) -- (A) -- (B) -- (C) retire the
+// finished rays.  Those are all the paths there are: the variants that were measured and rejected (a postponed leaf, a parked
+// triangle step) and the two hunt scaffolds are kept as profiles/r6/engine_experiments.patch, not as switches in this text.
 //
 // load(idx, o, d, tmax, tag) fetches queue entry idx; store(tag, hit, found) commits a finished ray.
 // lds: this lane's column of the workgroup's stack (stride kBlock dwords), 16 entries; deeper entries
@@ -155,15 +146,7 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
   bool have = false;
   bool any_l = ANY;                     // FRM: this lane's ray is an occlusion query (per lane); otherwise the template constant
 #define CRH_ISANY (FRM ? any_l : ANY)
-  uint32_t cur = kDone, tag = 0;
-  // PL (CRH_POSTPONE_LEAF): a triangle leaf the lane has reached but not tested yet.  The lane goes on with the next stack entry and takes part in the inner steps
-  // of its wavefront instead of waiting for the triangle phase; the leaf is tested there, BEFORE any leaf reached later (one at a time), so triangles are tested in
-  // the walk's order.  Boxes visited in between are pruned with the `best` of before that test: more visits (never counted: not in COUNT instantiations), the
-  // same hit -- a triangle in a box the up-to-date `best` would have culled lies strictly behind it (boxes are conservative), so it can neither win nor tie.
-  // Single-level walks only: a postponed leaf of an object must not be tested with the world ray the lane holds again after popping the object's sentinel.
-  constexpr bool PL = CRH_POSTPONE_LEAF != 0 && !COUNT && !TWO && (FRM || CRH_POSTPONE_LEAF > 1);
-  uint32_t pleaf = kDone;               // kDone: none
-#define CRH_LANE_DONE (cur == kDone && (!PL || pleaf == kDone))
+  uint32_t cur = kDone, tag = 0;        // cur == kDone: the lane's walk is over
   int sp = 0;
   v3 o = crh_mk3(0.f, 0.f, 0.f), d = o;
   // TWO: the world-space ray {origin, direction, reciprocal direction} of every lane waits in LDS while the lane walks inside an object
@@ -184,16 +167,22 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
   };
   float4 hit = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
   bool found = false;
-#if CRH_EXP_EARLY_TRI
-  // hunt scaffold (tests/hunts/two_level_anyhit_counting.py): round 4's early triangle fetch, compiled in behind a run-time switch that is never on
-  const bool early = gbox.w == -12345.0f;
-  float4 pre_a = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
   // donation state (DON): stack entries live in [sbase, sp); is_child: this lane walks a donated subtree, its total is absorbed by
   // its predecessor instead of stored; next: the lane that holds what comes right after this lane's part in traversal order;
   // chit / cfound: the folded totals of the successors absorbed so far (they come after everything this lane still walks)
   int sbase = 0; bool is_child = false, cfound = false; uint32_t next = kNoLane, head = 0;
   float4 chit = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+  // Ray start-up: the lane holds a new ray in o, d (FRM: any_l too) and starts its walk at the root, as the head of its own donation list.  ONE text for the two
+  // refills and the frame kernel's continuation; a macro, not a lambda: a call here costs every engine kernel registers (profiles/engine_cleanup.md).
+#define CRH_START_RAY(TMAX)                                                                                                    \
+  ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);                                                                    \
+  set_guard(gbox);                                                                                                             \
+  if (TWO) save_world();                                                                                                       \
+  best = TMAX; found = false; sp = 0; cur = root;                                                                              \
+  if (!FRM && ANY && TMAX < 0.f) cur = kDone;      /* second any-hit pass of a split scene: already occluded in the first (no visit, no test) */ \
+  if (TWO && t2.root2 != kQEmpty && touches_instances(t2, o, d, TMAX)) { lds[0] = t2.root2; sp = 1; }                          \
+  hit = make_float4(TMAX, 0.f, 0.f, __int_as_float(-1));                                                                       \
+  if (DON) { sbase = 0; is_child = false; cfound = false; next = kNoLane; head = lane; bound[lane] = __float_as_uint(TMAX); }
   // wave-uniform pool state.  Chunk per atomic: kPoolChunk for long queues (one cursor word sustains ~88 atomics/us); short
   // queues are cut finer so that every wavefront gets work -- a 75 K-ray launch in 256-ray chunks would keep 292 of the 5120
   // wavefronts busy with four 64-ray generations each (0.5 ms) instead of 1170 with one (CRH_POOL_DIV chunks per wavefront).
@@ -226,13 +215,8 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
         if (mine) {
           float tmax;
           load(base + (uint32_t)__popcll(idle & lt_mask), o, d, tmax, tag, any_l);
-          ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);
-          set_guard(gbox);
-          if (TWO) save_world();
-          best = tmax; found = false; sp = 0; cur = root; have = true; pleaf = kDone;
-          if (TWO && t2.root2 != kQEmpty && touches_instances(t2, o, d, tmax)) { lds[0] = t2.root2; sp = 1; }
-          hit = make_float4(tmax, 0.f, 0.f, __int_as_float(-1));
-          if (DON) { sbase = 0; is_child = false; cfound = false; next = kNoLane; head = lane; bound[lane] = __float_as_uint(tmax); }
+          have = true;
+          CRH_START_RAY(tmax)
         }
       }
     } else
@@ -253,14 +237,8 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
         if (mine) {
           float tmax;
           load(pool_next + rank, o, d, tmax, tag);
-          ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);
-          set_guard(gbox);
-          if (TWO) save_world();
-          best = tmax; found = false; sp = 0; cur = root; have = true; pleaf = kDone;
-          if (ANY && tmax < 0.f) cur = kDone;                      // second any-hit pass of a split scene: already occluded in the first (no visit, no test)
-          if (TWO && t2.root2 != kQEmpty && touches_instances(t2, o, d, tmax)) { lds[0] = t2.root2; sp = 1; }
-          hit = make_float4(tmax, 0.f, 0.f, __int_as_float(-1));
-          if (DON) { sbase = 0; is_child = false; cfound = false; next = kNoLane; head = lane; bound[lane] = __float_as_uint(tmax); }
+          have = true;
+          CRH_START_RAY(tmax)
         }
         pool_next += take;
         idle &= ~__ballot(mine);
@@ -318,7 +296,7 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
             ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);
             set_guard(gbox);
             if (TWO) save_world();
-            best = rbest; found = false; sbase = 0; sp = rcnt - 1; cur = lds[sp * kBlock]; have = true; pleaf = kDone;      // the nearest of the entries received
+            best = rbest; found = false; sbase = 0; sp = rcnt - 1; cur = lds[sp * kBlock]; have = true;      // the nearest of the entries received
             hit = make_float4(rbest, 0.f, 0.f, __int_as_float(-1));
             is_child = true; cfound = false; next = rnext; head = rhead;            // ... and before what the donor gave away earlier
             if (FRM) any_l = rany != 0;
@@ -466,11 +444,7 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
     // one ray/triangle test of this lane against leaf-order triangle `ti`
     auto tri_step = [&](uint32_t ti) {
       const float4* tp = tris + kTriStride * ti;
-#if CRH_EXP_EARLY_TRI
-      const float4 a = early ? pre_a : tp[0], b = tp[1], c = tp[2];
-#else
       const float4 a = tp[0], b = tp[1], c = tp[2];
-#endif
       if (COUNT || (FRM && CRH_FRAME_STATS)) ++n_tris;
 #if CRH_FRAME_STATS
       if (FRM && lane == (uint32_t)__ffsll((long long)__ballot(true)) - 1u) ++fs_tri_w;
@@ -496,21 +470,12 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
 #if CRH_INNER_STEPS > 0
     // (the frame kernel's rays -- every bounce mixed in one wavefront -- hold leaves less often: three inner steps per turn there, lone frame 3.15 -> 3.05 ms on C3)
     constexpr int kInnerSteps = FRM ? CRH_INNER_STEPS + 1 : CRH_INNER_STEPS;
-#if CRH_POSTPONE_LEAF || CRH_HUNT_NOOP_CALLS
-    // PL: a triangle leaf in hand moves aside (if none waits yet) and the lane descends on
-    auto postpone = [&]() { if (PL && have && (cur & kQLeafBit) && cur != kDone && pleaf == kDone) { pleaf = cur; pop(); } };
-    postpone();
-#pragma unroll 1
-    for (int step_ = 0; step_ < kInnerSteps && have && !(cur & kQLeafBit); ++step_) { inner_step(); postpone(); }
-#else
+    // nothing but inner_step() is called in or around this loop: calls of a lambda that does nothing here made hipcc miscompile the two-level counting any-hit
+    // kernel (profiles/r6/engine_experiments.patch brings that build back)
 #pragma unroll 1
     for (int step_ = 0; step_ < kInnerSteps && have && !(cur & kQLeafBit); ++step_) inner_step();
-#endif
 #else
     while (have && !(cur & kQLeafBit)) inner_step();
-#endif
-#if CRH_EXP_EARLY_TRI
-    if (early && have && (cur & kQLeafBit) && cur != kDone && (cur & 0xF0000000u) != CRH_REF_INSTANCE_TAG) pre_a = tris[kTriStride * (cur & 0x0FFFFFFFu)];
 #endif
     CRH_FS_MARK(fc_inner)
     // ------------------------------------------------------------------ (B) the leaf in hand
@@ -530,20 +495,6 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
       ++sp;
       cur = __float_as_uint(meta.x);
     }
-#if CRH_FRAME_PARK > 0
-    else if (FRM && !TWO && (uint32_t)__popcll(__ballot(have && (cur & kQLeafBit) && cur != kDone)) < (uint32_t)CRH_FRAME_PARK && __ballot(have && !(cur & kQLeafBit)) != 0ull) {
-      // parked: too few leaves in hand and somebody can still descend -- the leaves wait for the next turn
-    }
-#endif
-#if CRH_POSTPONE_LEAF
-    else if (PL) {
-      if (have && pleaf != kDone) {
-        tri_step(pleaf & 0x0FFFFFFFu);                           // the postponed leaf first: triangles in the walk's order
-        pleaf = kDone;
-        if (CRH_ISANY && found) cur = kDone;                     // an occluder ends the walk (what pop() does in the plain form)
-      }
-    }
-#endif
     else if (have && (cur & kQLeafBit) && cur != kDone) {
       tri_step(cur & 0x0FFFFFFFu);                               // one triangle per leaf (crh_bvh_format.h)
       pop();
@@ -552,12 +503,13 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
     CRH_FS_MARK(fc_leaf)
     // ------------------------------------------------------------------ (C) retire finished rays
 #if CRH_FRAME_STATS
-    if (FRM) { const unsigned long long fm_ = __ballot(have && CRH_LANE_DONE); if (fm_ != 0ull) { ++fs_store_w; fs_fin += (uint32_t)__popcll(fm_); } }
+    if (FRM) { const unsigned long long fm_ = __ballot(have && cur == kDone); if (fm_ != 0ull) { ++fs_store_w; fs_fin += (uint32_t)__popcll(fm_); } }
 #endif
+    bool fin = have && cur == kDone;                                   // this lane's result is stored now (DON: only once the parts given away are folded in, below)
     if (DON) {
       // own part walked and no successor left: fold what was absorbed behind the own hit (left-biased minimum: a later part
       // wins only with a strictly smaller t); helpers then wait to be absorbed by their predecessor, the head stores
-      const bool finished = have && CRH_LANE_DONE && next == kNoLane;
+      const bool finished = have && cur == kDone && next == kNoLane;
       if (finished && cfound) { if (CRH_ISANY || !found || chit.x < hit.x) { hit = chit; found = true; } cfound = false; }
       const unsigned long long fin_children = __ballot(finished && is_child);
       if (fin_children != 0ull) {
@@ -572,46 +524,21 @@ __device__ __forceinline__ void trace_engine(const float4* __restrict__ nodes, c
         }
         if ((fin_children >> lane) & 1ull) { have = false; is_child = false; }           // absorbed: the lane is free again
       }
-      const bool fin = have && !is_child && CRH_LANE_DONE && next == kNoLane;
+      fin = have && !is_child && cur == kDone && next == kNoLane;      // the head of a list whose parts are all folded in
       if (fin && cfound) { if (CRH_ISANY || !found || chit.x < hit.x) { hit = chit; found = true; } cfound = false; }
-      if constexpr (FRM) {
-        float tmax = CRH_MAXFLOAT;
-        const bool go_on = store(fin, tag, hit, found, any_l, o, d, tmax);      // the whole wavefront calls; true: the lane's path continues with the ray in o, d
-        if (fin) {
-          have = go_on;
-          if (go_on) {
-            any_l = false;
-            ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);
-            set_guard(gbox);
-            if (TWO) save_world();
-            best = tmax; found = false; sp = 0; cur = root; pleaf = kDone;
-            if (TWO && t2.root2 != kQEmpty && touches_instances(t2, o, d, tmax)) { lds[0] = t2.root2; sp = 1; }
-            hit = make_float4(tmax, 0.f, 0.f, __int_as_float(-1));
-            sbase = 0; is_child = false; cfound = false; next = kNoLane; head = lane; bound[lane] = __float_as_uint(tmax);
-          }
-        }
-      } else if (fin) { store(tag, hit, found); have = false; }
-    } else if constexpr (FRM) {
-      const bool fin = have && CRH_LANE_DONE;
+    }
+    if constexpr (FRM) {
       float tmax = CRH_MAXFLOAT;
       const bool go_on = store(fin, tag, hit, found, any_l, o, d, tmax);        // the whole wavefront calls; true: the lane's path continues with the ray in o, d
       if (fin) {
         have = go_on;
-        if (go_on) {
-          any_l = false;
-          ix = inv_dir(d.x); iy = inv_dir(d.y); iz = inv_dir(d.z);
-          set_guard(gbox);
-          if (TWO) save_world();
-          best = tmax; found = false; sp = 0; cur = root; pleaf = kDone;
-          if (TWO && t2.root2 != kQEmpty && touches_instances(t2, o, d, tmax)) { lds[0] = t2.root2; sp = 1; }
-          hit = make_float4(tmax, 0.f, 0.f, __int_as_float(-1));
-        }
+        if (go_on) { any_l = false; CRH_START_RAY(tmax) }
       }
-    } else { if (have && CRH_LANE_DONE) { store(tag, hit, found); have = false; } }
+    } else if (fin) { store(tag, hit, found); have = false; }
     CRH_FS_MARK(fc_retire)
   }
 #undef CRH_ISANY
-#undef CRH_LANE_DONE
+#undef CRH_START_RAY
 #if CRH_FRAME_STATS
   if (FRM) {
     const uint32_t li = wave_sum(n_nodes), lt = wave_sum(n_tris);

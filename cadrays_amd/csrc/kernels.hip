@@ -112,9 +112,9 @@ void launch_trace_any(const Launch& L, const DScene& S, const DPaths& P, const D
 // The frame kernel (k_frame.h): ray generation, every bounce's traversal and shading of a small batch in ONE launch.  `ctl`: two words, zero at launch (the kernel
 // leaves them zero).  The grid is what the register budget keeps resident (every workgroup is a persistent streaming path tracer), or less for a frame that
 // shares the chip with others in flight.
-// LDS of the frame kernel: stack 16 x 1024 x 4 B = 64 KB + two rings of kFrameRing x 4 B = 32 KB + bounds 4 KB + materials 4 KB = ~104 KB (two-level scenes: + 36 KB of
-// world rays = ~140 KB).  Only a part with gfx950's 160 KB of LDS per compute unit can launch it.
-static_assert((size_t)kLdsStack * kFrameBlock * 4 + (2 + CRH_FRAME_MISS_RING) * (size_t)kFrameRing * 4 + (size_t)kFrameBlock * 4 + (size_t)kFrameMats * 128 + 9 * (size_t)kFrameBlock * 4 <= 160 * 1024, "k_frame<true> does not fit the LDS of a gfx950 compute unit");
+// LDS of the frame kernel: stack 16 x 1024 x 4 B = 64 KB + three rings of kFrameRing x 4 B = 48 KB + bounds 4 KB + materials 4 KB = ~120 KB (two-level scenes: + 36 KB of
+// world rays = ~156 KB).  Only a part with gfx950's 160 KB of LDS per compute unit can launch it.
+static_assert((size_t)kLdsStack * kFrameBlock * 4 + 3 * (size_t)kFrameRing * 4 + (size_t)kFrameBlock * 4 + (size_t)kFrameMats * 128 + 9 * (size_t)kFrameBlock * 4 <= 160 * 1024, "k_frame<true> does not fit the LDS of a gfx950 compute unit");
 static int frame_occupancy(bool two_level)
 {
   static int per_cu[2] = {0, 0};
