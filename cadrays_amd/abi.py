@@ -155,6 +155,27 @@ class crh_view_params(C.Structure):
 VIEW_AUTO, VIEW_NEAREST, VIEW_BILINEAR, VIEW_AREA = 0, 1, 2, 3      # crh_view_params.filter
 VIEW_MAX_SIDE = 8192
 
+class crh_annot_segment(C.Structure):
+    """one annotation segment (include/cadrays_hip.h): world-space end points, colour, alpha, style = width (bits 0-3) | mode << 8"""
+    _fields_ = [("a", C.c_float * 3), ("b", C.c_float * 3), ("rgb", C.c_uint8 * 3), ("alpha", C.c_uint8), ("style", C.c_uint32)]
+
+
+class crh_annot_params(C.Structure):
+    """the annotations' parameters (include/cadrays_hip.h; crh_annot_defaults fills them: ANNOT_DEFAULTS below)"""
+    _fields_ = [("depth_bias", C.c_float), ("hidden_alpha", C.c_uint32)]
+
+
+ANNOT_ON_TOP, ANNOT_HIDE, ANNOT_XRAY = 0, 1, 2      # the mode in bits 8-9 of crh_annot_segment.style
+ANNOT_MAX_SEGMENTS = 65536
+ANNOT_SEGMENT_DTYPE = [("a", "<f4", (3,)), ("b", "<f4", (3,)), ("rgb", "u1", (3,)), ("alpha", "u1"), ("style", "<u4")]      # numpy view of the list (32 B)
+ANNOT_RECORD_DTYPE = [("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("q0", "<f4"), ("q1", "<f4"), ("flags", "<u4"), ("pad", "<u4")]      # ... of the screen records (32 B)
+
+
+def annot_style(width=1, mode=ANNOT_ON_TOP):
+    """CRH_ANNOT_STYLE: the style word of a segment `width` pixels wide drawn in `mode`"""
+    return int(width) | (int(mode) << 8)
+
+
 _f32 = lambda x: C.c_float(x).value      # the defaults as the float32 fields hold them, so that get_spec() == SPEC_DEFAULTS
 SPEC_DEFAULTS = dict(uniform_32bit=0, texel_gamma2=0, mis_single_lobe=0, eps_rule=0, eta_no_dielectric=1.0,
                      rr_start_bounce=3, rr_survival_cap=_f32(0.95), min_contribution=_f32(1.0e-2), min_throughput=_f32(1.0e-3), raygen_bilinear=0, env_orientation=0, display_gamma22=0)
@@ -171,6 +192,8 @@ VIEW_DEFAULTS = dict(width=0, height=0, src=(0, 0, 0, 0), filter=VIEW_AUTO, rese
 
 REPROJECT_DEFAULTS = dict(max_history=16.0, until_samples=64, normal_cos=_f32(0.9063077870366499), depth_ratio=_f32(1.05))      # cos 25 deg
 
+ANNOT_DEFAULTS = dict(depth_bias=2.0 ** -9, hidden_alpha=64)
+
 REPROJECT_MOTION_DEFAULTS = dict(max_history_moved=16.0, max_history_static=8.0)
 
 assert C.sizeof(crh_outline_params) == 20 and C.sizeof(crh_denoise_params) == 16
@@ -178,6 +201,7 @@ assert C.sizeof(crh_shade_guide_params) == 16 and C.sizeof(crh_shade_guide_scene
 assert C.sizeof(crh_reproject_params) == 16 and C.sizeof(crh_reproject_frame) == 64
 assert C.sizeof(crh_reproject_motion_params) == 8
 assert C.sizeof(crh_view_params) == 32
+assert C.sizeof(crh_annot_segment) == 32 and C.sizeof(crh_annot_params) == 8
 assert C.sizeof(crh_meter_params) == 40 and C.sizeof(crh_meter_result) == 1044
 assert C.sizeof(crh_fit_result) == 84
 assert C.sizeof(crh_region_stats) == 32
@@ -206,4 +230,6 @@ EXPORTS = [
     "crh_reproject_defaults", "crh_set_reproject", "crh_get_reproject", "crh_read_reprojected", "crh_bench_reproject", "crh_reproject_frame_host", "crh_reproject_host",
     "crh_reproject_motion_defaults", "crh_set_reproject_motion", "crh_get_reproject_motion", "crh_get_reproject_launches", "crh_bench_reproject_motion", "crh_reproject_delta_host", "crh_reproject_motion_host",
     "crh_read_view", "crh_read_view_begin", "crh_read_view_end", "crh_view_host", "crh_view_fit", "crh_view_to_frame", "crh_bench_view",
+    "crh_annot_defaults", "crh_set_annotations", "crh_get_annotations", "crh_read_annotation_ids", "crh_pick_annotation", "crh_read_annotation_records", "crh_bench_annotations",
+    "crh_annot_project_host", "crh_annot_draw_host",
 ]

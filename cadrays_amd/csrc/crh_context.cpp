@@ -197,6 +197,8 @@ static const EnvKnob kEnvKnobs[] = {
   {"CRH_SPLIT_PASSES",       "split scenes (static tree + moved objects): 0 one walk in the two-level kernels, 1 two traversal passes, unset: by the number of moved objects"},
   {"CRH_DENOISE_STAGED",     "denoised display: 0: the passes of step 1 and 2 take the plain gather kernel instead of the LDS-staged one (default 1: staged, 13 - 15 % faster per pass at 1080p, profiles/denoise_ab.md; the same bytes either way)"},
   {"CRH_REPROJECT_STAGED",   "per-object history deltas: 1: the motion kernel stages the moved objects' records in LDS while at most 64 are flagged (default 0: the plain form; the staged one measured no faster, profiles/reproject_ab.md; the same bytes either way)"},
+  {"CRH_ANNOT_TILE",         "annotations: edge of the drawing kernel's tile, one workgroup each: 8, 16 or 32 pixels (default 16, the fastest measured; the same bytes either way, DESIGN.md section 6.15)"},
+  {"CRH_ANNOT_BIN",          "annotations: how the per-tile bins are filled: gather = one thread per tile and word of the list, scatter = one thread per segment with atomicOr into a cleared buffer (default: gather up to 256 segments, scatter above, DESIGN.md section 6.15; the same bits either way)"},
   {"CRH_REDUCE_RCCL_SINGLE", "crh_reduce sends even a one-context group through RCCL (exercises the library binding on a 1-GPU box)"},
 };
 
@@ -235,6 +237,8 @@ static void read_env(crh_ctx* c)
   if (const char* e = getenv("CRH_FRAME_PIPE")) { int v = atoi(e); if (v >= 1 && v <= 8) c->frame_pipe_depth = (uint32_t)v; }
   if (const char* e = getenv("CRH_DENOISE_STAGED")) c->dn_staged = atoi(e) != 0;
   if (const char* e = getenv("CRH_REPROJECT_STAGED")) c->rpm_staged = atoi(e) != 0;
+  if (const char* e = getenv("CRH_ANNOT_TILE")) { int v = atoi(e); if (v == 8 || v == 16 || v == 32) c->an_tile = (uint32_t)v; }
+  if (const char* e = getenv("CRH_ANNOT_BIN")) c->an_bin_form = !strcmp(e, "scatter") ? 2 : !strcmp(e, "gather") ? 1 : 0;
   if (const char* e = getenv("CRH_LANES")) { int v = atoi(e); if (v >= 1 && v <= 8) c->n_lanes = (uint32_t)v; }
 }
 

@@ -22,6 +22,8 @@
 //                      (reproject_kernels.hip), the capture in crh_set_camera, the host-only twin
 //   crh_view.cpp       the viewport read-out: the finished RGB8 frame resampled to the window's size as the LAST stage of the display chain (view_kernels.hip),
 //                      the letterbox fit, the window-to-frame mapping, the host-only twin
+//   crh_annotate.cpp   annotations: world-space line segments projected, binned and drawn over the frame as the last stage of the display chain, hidden or
+//                      dimmed where the id buffer says the scene is nearer (annotate_kernels.hip), the queries, the host-only twins
 //   crh_debug.cpp      API-level ray tracing, micro-benchmarks and the math / BSDF test hooks
 //
 // Shared by those, below: display_source (the image a read-out shows), grow_display_scratch, geometry_changed / geom_gen and side_upload (the tables derived from the
@@ -347,6 +349,27 @@ struct ViewState {
   DevBuf<uint8_t> d_vw_full[2];
 };
 
+// ---- annotations (crh_annotate.cpp): display state like the selection -- only the LDR read-outs (and the annotation queries) look at it.  The list lives on the host
+// and, from the first read-out that draws it, on the device.  The records and the per-tile bins are DERIVED from the list, the camera and the frame size: one pair per
+// SET -- 0 the context's stream, 1 the read-back stream, as the denoise filter has them, 2 the id buffer's stream for the queries -- each with the stamp of what it was
+// computed from, recomputed in stream order by the first use after a change.  A host that never hands over a list pays nothing.
+struct AnnotStamp {
+  uint64_t gen = 0; crh_camera cam{}; uint32_t w = 0, h = 0, tile = 0, scatter = 0; uint64_t ids_gen = 0;      // gen 0: none
+  bool operator==(const AnnotStamp& o) const { return gen == o.gen && !std::memcmp(&cam, &o.cam, sizeof cam) && w == o.w && h == o.h && tile == o.tile && scatter == o.scatter && ids_gen == o.ids_gen; }
+};
+struct AnnotateState {
+  bool an_on = false; crh_annot_params an_par{}; std::vector<crh_annot_segment> an_segs;
+  uint64_t an_gen = 0;            // THE LIST'S GENERATION: bumped by every crh_set_annotations that is accepted
+  bool an_depth = false;          // some segment has mode HIDE or XRAY: the drawing reads the id buffer
+  DevBuf<void> d_an_segs; uint64_t an_segs_gen = 0;      // (the generation the device copy holds)
+  DevBuf<void> d_an_rec[3]; DevBuf<uint32_t> d_an_bins[3]; AnnotStamp an_stamp[3];
+  DevBuf<int32_t> d_an_ids; DevBuf<float> d_an_s; AnnotStamp an_plane_stamp;      // the id plane and the parameter plane of the queries
+  uint32_t an_tile = 16;          // the tile edge of the drawing kernel (CRH_ANNOT_TILE=8|16|32): 16 draws fastest, 8 costs 1.3 - 1.5 times as much
+  int an_bin_form = 0;            // the binning form: 0 by the list's length -- gather (a thread per tile and word) up to kAnnotGatherMax segments, scatter (a thread per segment,
+                                  // atomicOr) above: the gather form costs 3 (1080p) / 13 (4K) us per word of the list, the scatter form 16 - 120 us whatever the length --
+                                  // 1 gather, 2 scatter (CRH_ANNOT_BIN=gather|scatter); the same bits either way
+};
+
 // ---- counters and timing
 struct TimingState {
   bool counters_on = false, timing_on = false;
@@ -357,7 +380,7 @@ struct TimingState {
 
 }  // namespace crh
 
-struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ShadeGuideState, crh::ReprojectState, crh::ViewState, crh::TimingState {
+struct crh_ctx : crh::HostInputs, crh::TwoLevelState, crh::BuiltScene, crh::FrameState, crh::ScheduleState, crh::ReadbackState, crh::PickState, crh::FitState, crh::RegionState, crh::OutlineState, crh::DenoiseState, crh::ShadeGuideState, crh::ReprojectState, crh::ViewState, crh::AnnotateState, crh::TimingState {
   int device = 0;
   uint64_t geom_gen = 1;  // THE GEOMETRY GENERATION: geometry_changed() bumps it; every table derived from pos / tri / tri_obj remembers the one it was built from (0: none yet)
   hipStream_t stream_ = nullptr;   // use cstream(c): it first joins frames still in flight on the pipeline streams
@@ -559,6 +582,10 @@ int read_end(crh_ctx* c, void* out, ReadKind kind);
 // ---- crh_view.cpp
 // The resample of the frame at d_full (W x H of the parameters in force) into d_out, enqueued on `on`
 int view_resample(crh_ctx* c, hipStream_t on, const uint8_t* d_full, const ViewPlan& P, uint8_t* d_out);
+// ---- crh_annotate.cpp
+// Annotations over the finished bytes of the FRAME at d_ldr, enqueued on `on` (set: whose records and bins), LAST in the display chain, behind overlay_ldr; nothing at
+// all while the feature is off, the list is empty or there is no scene
+int annotate_ldr(crh_ctx* c, hipStream_t on, int set, uint8_t* d_ldr);
 // ---- crh_reduce.cpp
 void release_comms(crh_ctx* c);
 int reduce_fake_devices(crh_ctx* const* ctxs, uint32_t n, uint32_t root);      // crh_reduce.cpp: the RCCL branch of crh_reduce on contexts that share a device (test hook)

@@ -58,7 +58,8 @@ int enqueue_display_chain(crh_ctx* c, const Launch& L, int set, int block, uint8
   if (int rc = denoise_src(c, L.stream, shown, set, &shown)) return rc;   // ... the denoised display (crh_denoise.cpp): `src` itself, and nothing at all, while the feature is off
   launch_tonemap(L, shown, d_ldr, n, c->par.tonemap_mode, c->par.exposure, c->par.white_point, c->spec.display_gamma22, tiles ? c->d_picked : nullptr, c->par.width, ts, metered);
   if (int rc = outline_ldr(c, L.stream, d_ldr)) return rc;                // feature lines (crh_outline.cpp): nothing at all while the feature is off
-  return overlay_ldr(c, L.stream, d_ldr);                                 // hover / selection (crh_pick.cpp): last, and nothing at all when neither is set
+  if (int rc = overlay_ldr(c, L.stream, d_ldr)) return rc;                // hover / selection (crh_pick.cpp): nothing at all when neither is set
+  return annotate_ldr(c, L.stream, set, d_ldr);                           // annotations (crh_annotate.cpp): LAST, and nothing at all while there is no list
 }
 
 // Asynchronous read-back of the frame as submitted so far -- LDR (tone-mapped RGB8), HDR (linear float RGB) or a VIEW of the LDR frame (crh_view.cpp: the frame goes

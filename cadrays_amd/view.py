@@ -216,6 +216,64 @@ class View(Backend):
         """set_transforms drops the history again, as in a view that never called SetReprojectMotion"""
         self.set_reproject_motion(False)
 
+    # ---- annotations: world-space segments over the display, depth-tested (crh_annotate.cpp; the reference paints its helpers with ImGui, ImRaytraceControls.cxx:64, :93-111) ----
+    def SetAnnotations(self, segments, depth_bias=abi.ANNOT_DEFAULTS["depth_bias"], hidden_alpha=abi.ANNOT_DEFAULTS["hidden_alpha"]):
+        """draw this list (a record array of abi.ANNOT_SEGMENT_DTYPE: cadrays_amd.annotations builds them) over every LDR read-out from now on, each segment hidden,
+        dimmed or left on top where the scene is nearer; nothing restarts.  An empty list switches the feature off."""
+        sg = _annot_list(segments)
+        p = abi.crh_annot_params(float(depth_bias), int(hidden_alpha))
+        self._call("set_annotations", sg.ctypes.data_as(C.POINTER(abi.crh_annot_segment)) if len(sg) else None, C.c_uint32(len(sg)), C.byref(p))
+
+    def ClearAnnotations(self):
+        """no annotations: the LDR bytes of a view that never called SetAnnotations"""
+        self._call("set_annotations", None, C.c_uint32(0), None)
+
+    def GetAnnotations(self):
+        """dict(segments, depth_bias, hidden_alpha, on): the list and the parameters in force (the defaults while the feature is off)"""
+        n, on, p = C.c_uint32(0), C.c_int(0), abi.crh_annot_params()
+        self._call("get_annotations", None, C.c_uint32(0), C.byref(n), C.byref(p), C.byref(on))
+        sg = np.zeros(n.value, abi.ANNOT_SEGMENT_DTYPE)
+        self._call("get_annotations", sg.ctypes.data_as(C.POINTER(abi.crh_annot_segment)) if len(sg) else None, C.c_uint32(len(sg)), None, None, None)
+        return {"segments": sg, "depth_bias": np.float32(p.depth_bias), "hidden_alpha": int(p.hidden_alpha), "on": bool(on.value)}
+
+    def ReadAnnotationIds(self):
+        """(H, W) int32: per pixel the index of the last segment that drew there (an x-ray pixel counts), or -1"""
+        out = np.empty((self.height, self.width), np.int32)
+        self._call("read_annotation_ids", out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    def PickAnnotation(self, x, y):
+        """the hit test for a handle: (segment index or -1, the parameter s along that segment's clipped screen record at the pixel)"""
+        seg, s = C.c_int32(-1), C.c_float(0.0)
+        self._call("pick_annotation", C.c_uint32(int(x)), C.c_uint32(int(y)), C.byref(seg), C.byref(s))
+        return int(seg.value), np.float32(s.value)
+
+    def ReadAnnotationRecords(self):
+        """the projected records as the device computed them for the camera in force: a record array of abi.ANNOT_RECORD_DTYPE, one per segment"""
+        n = C.c_uint32(0)
+        self._call("get_annotations", None, C.c_uint32(0), C.byref(n), None, None)
+        out = np.zeros(n.value, abi.ANNOT_RECORD_DTYPE)
+        self._call("read_annotation_records", out.ctypes.data_as(C.c_void_p) if len(out) else None)
+        return out
+
+    def BenchAnnotations(self, repeats=20):
+        """crh_bench_annotations: dict(project_ms, bin_ms, draw_ms), device time per launch of the three kernels for the list in force"""
+        a, b, d = C.c_float(0), C.c_float(0), C.c_float(0)
+        self._call("bench_annotations", C.c_uint32(int(repeats)), C.byref(a), C.byref(b), C.byref(d))
+        return {"project_ms": a.value, "bin_ms": b.value, "draw_ms": d.value}
+
+    def ShowSelectionBox(self, extra=None, **style):
+        """the bounding box of the selection (crh_get_selection_bounds: the manipulator's pivot box, AppViewer.cxx:863-875) as the annotation list, in front of the
+        segments of `extra`; nothing selected: `extra` alone (an empty list switches the feature off).  Returns the list that was set."""
+        from . import annotations
+        parts = [] if extra is None else [_annot_list(extra)]
+        if self._selected:
+            lo, hi = self.selection_bounds()
+            parts.insert(0, annotations.box(lo, hi, **style))
+        sg = annotations.join(*parts)
+        self.SetAnnotations(sg)
+        return sg
+
     # ---- V3d_View::FitAll / ZFitAll (crh_fit.cpp) --------------------------------------------------
     def _fit(self, chosen, margin):
         fields, r = self.fit_view(self._n_objects, chosen, margin)
@@ -743,6 +801,52 @@ def view_to_frame(frame_w, frame_h, vx, vy, width, height, src=(0, 0, 0, 0), fil
     if rc != 0:
         raise BackendError(f"crh_view_to_frame -> {rc}")
     return int(fx.value), int(fy.value)
+
+
+def _annot_list(segments):
+    """a contiguous record array of abi.ANNOT_SEGMENT_DTYPE (an empty one for None)"""
+    return np.zeros(0, abi.ANNOT_SEGMENT_DTYPE) if segments is None else np.ascontiguousarray(segments, abi.ANNOT_SEGMENT_DTYPE).reshape(-1)
+
+
+def annot_project_host(cam, width, height, segments):
+    """crh_annot_project_host on the host only (no GPU): the screen records of the segments under a scenes.Camera at a frame size, a record array of
+    abi.ANNOT_RECORD_DTYPE"""
+    from .binding import camera_struct
+    lib = load_library()
+    sg = _annot_list(segments)
+    out = np.zeros(len(sg), abi.ANNOT_RECORD_DTYPE)
+    rc = lib.crh_annot_project_host(C.byref(camera_struct(cam)), C.c_uint32(int(width)), C.c_uint32(int(height)),
+                                    sg.ctypes.data_as(C.POINTER(abi.crh_annot_segment)) if len(sg) else None, C.c_uint32(len(sg)),
+                                    out.ctypes.data_as(C.c_void_p) if len(sg) else None)
+    if rc != 0:
+        raise BackendError(f"crh_annot_project_host -> {rc}")
+    return out
+
+
+def annot_draw_host(records, segments, cam, width, height, ldr=None, rays=None, t_px=None, depth_bias=abi.ANNOT_DEFAULTS["depth_bias"],
+                    hidden_alpha=abi.ANNOT_DEFAULTS["hidden_alpha"]):
+    """crh_annot_draw_host on the host only (no GPU): the segments drawn over a copy of the (H, W, 3) uint8 image `ldr` (None: no image) from their records; rays
+    (H * W, 8) as camera_rays returns them for the pixels in row-major order and t_px (H, W) as read_ids returns it (both None when no segment asks for depth).
+    Returns (image or None, (H, W) int32 id plane)."""
+    from .binding import camera_struct
+    lib = load_library()
+    sg = _annot_list(segments)
+    rec = np.ascontiguousarray(records, abi.ANNOT_RECORD_DTYPE).reshape(-1)
+    assert len(rec) == len(sg)
+    W, H = int(width), int(height)
+    img = None if ldr is None else np.array(ldr, np.uint8, order="C")
+    assert img is None or img.shape == (H, W, 3)
+    r = None if rays is None else np.ascontiguousarray(rays, np.float32).reshape(H * W, 8)
+    t = None if t_px is None else np.ascontiguousarray(t_px, np.float32).reshape(H, W)
+    ids = np.empty((H, W), np.int32)
+    p = abi.crh_annot_params(float(depth_bias), int(hidden_alpha))
+    fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+    rc = lib.crh_annot_draw_host(rec.ctypes.data_as(C.c_void_p) if len(sg) else None, sg.ctypes.data_as(C.POINTER(abi.crh_annot_segment)) if len(sg) else None,
+                                 C.c_uint32(len(sg)), C.byref(p), C.byref(camera_struct(cam)), C.c_uint32(W), C.c_uint32(H), fp(r), fp(t),
+                                 None if img is None else img.ctypes.data_as(C.POINTER(C.c_uint8)), ids.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise BackendError(f"crh_annot_draw_host -> {rc}")
+    return img, ids
 
 
 def build_bvh_host(pos, tri, threads=0):

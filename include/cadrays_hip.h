@@ -951,6 +951,87 @@ CRH_API int crh_view_to_frame(const crh_view_params* p, uint32_t W, uint32_t H, 
  * identity parameters too (a copy).  Synchronous; changes nothing a read-out could see.  The refusals of crh_read_view, and repeats == 0. */
 CRH_API int crh_bench_view(crh_ctx* ctx, const crh_view_params* p, uint32_t repeats, float* resample_ms);
 
+/* --- annotations: world-space line segments over the display, depth-tested (crh_annotate.cpp, cadrays_amd/csrc/annotate_kernels.hip) ------------------
+ * The helpers an application draws over the path-traced frame -- the manipulator at the selection's pivot (ImGuizmo::Manipulate, reference
+ * src/ImGui/ImRaytraceControls.cxx:64), a marker at every positional light (DrawLights, :93-111), a ground grid, an axis triad, the selection's box, dimension lines
+ * -- all reduce to one primitive: a list of coloured WORLD-SPACE SEGMENTS.  The reference paints them with ImGui on top of the image, with no notion of what the scene
+ * hides; here the LDR read-outs (crh_read_ldr, crh_read_ldr_begin / _end, crh_read_view*; ONLY those) project, bin and draw the list as the LAST stage of the frame's
+ * display chain -- after the feature lines, the selection and the hover, so a handle keeps its own colour over a tinted selection -- and each segment is hidden,
+ * dimmed or left on top where the first-hit id buffer says the scene is nearer.  Display state like the selection: nothing restarts, the HDR image, the
+ * accumulator, the frame counter, crh_stats, the id buffer, crh_read_outline and crh_read_denoised are what they would have been without it.  Off (the state of a new
+ * context), an empty list, or no built scene: nothing is allocated, nothing is launched, the bytes are those of a context that never heard of the feature.
+ *
+ *   THE PROJECTION of a segment (a, b), in float64 from the widened floats, every operation rounded on its own, no fused multiply-add:
+ *     1  right, up, fwd, tan_half, aspect: the camera frame crh_render derives (crh_reproject_frame_host hands it out).  v = P - eye;
+ *        xr = (v.x r.x + v.y r.y) + v.z r.z with r = right, yu likewise with up, z with fwd
+ *     2  near clip: zmax = max(za, zb); !(zmax > 0): the record is INVALID (nothing is drawn).  zmin = zmax * 2^-16 (perspective) or 0 (orthographic).  The end point
+ *        with z < zmin moves along the segment to z = zmin:  u = (zmin - z) / (z_other - z), xr += u (xr_other - xr), yu += u (yu_other - yu), z = zmin
+ *     3  continuous pixel coordinates, a pixel centre at px + 0.5, row 0 the top:  kx = tan_half * aspect, ky = tan_half;  perspective dx = z kx, dy = z ky;
+ *        orthographic dx = ortho_scale * aspect, dy = ortho_scale;   X = (xr / dx + 1) (W / 2),  Y = (1 - yu / dy) (H / 2)
+ *        depth coordinate, linear along the SCREEN segment:  q = 1 / z (perspective), q = z (orthographic)
+ *     4  Liang-Barsky against the guard band [-W, 2W] x [-H, 2H] -- edges left, right, top, bottom; per edge with p t <= q:  p == 0: outside iff q < 0; r = q / p;
+ *        p < 0: r > t1 outside, else t0 = max(t0, r);  p > 0: r < t0 outside, else t1 = min(t1, r) -- over (t0, t1) = (0, 1), D = B - A:
+ *        a' = A + t0 D where t0 > 0, b' = A + t1 D where t1 < 1, else the point itself; q with the same parameter; nothing left: INVALID;
+ *        one of the six not finite: INVALID; then x = min(max(x, -W), 2W), y = min(max(y, -H), 2H) (max first; the sum can leave the band by its rounding)
+ *     5  all six rounded to float32; one of them not finite: INVALID;  record {x0, y0, x1, y1, q0, q1, flags (bit 0: valid), pad}, 32 B; invalid = all zero
+ *     The projection goes through the pixel-centre pinhole, as the id buffer does: a lens does not widen a line, and crh_spec.raygen_bilinear is not followed.
+ *   THE PIXEL RULE, float32, no fused multiply-add, for pixel (x, y):  p = (x + 0.5, y + 0.5), a = (x0, y0), e = (x1 - x0, y1 - y0), l2 = e.x e.x + e.y e.y;
+ *        s = l2 > 0 ? min(max(((p.x - a.x) e.x + (p.y - a.y) e.y) / l2, 0), 1) : 0;   d = p - (a + s e);   COVERED iff d.x d.x + d.y d.y <= (width * 0.5)^2
+ *     depth (modes HIDE and XRAY):  zh = t (d . fwd) -- t the pixel's first-hit distance (crh_read_ids), d the direction of its ray (crh_camera_rays),
+ *        d . fwd = (d.x f.x + d.y f.y) + d.z f.z; orthographic: zh = t --  qs = q0 + s (q1 - q0),  zb = zh (1 + depth_bias);
+ *        perspective: OCCLUDED iff qs zb < 1;  orthographic: OCCLUDED iff qs > zb;  a miss (t >= 1e15) never occludes
+ *     composite, segments in ascending index, per channel  ldr = (ldr (256 - A) + colour A + 128) >> 8  with  A = alpha where the pixel is visible or the mode is
+ *        ON_TOP,  A = (alpha hidden_alpha + 128) >> 8  for an occluded XRAY pixel; an occluded HIDE pixel is skipped and does not enter the id plane
+ *   a == b is a point marker: a disc of the width.  No result depends on the bins the device sorts the records into. */
+#define CRH_ANNOT_ON_TOP 0u      /* drawn whatever the scene hides                          */
+#define CRH_ANNOT_HIDE   1u      /* occluded pixels are not drawn                           */
+#define CRH_ANNOT_XRAY   2u      /* occluded pixels are drawn with the hidden alpha         */
+#define CRH_ANNOT_MAX_SEGMENTS 65536u
+#define CRH_ANNOT_STYLE(width, mode) ((uint32_t)(width) | ((uint32_t)(mode) << 8))
+typedef struct crh_annot_segment {
+  float    a[3], b[3];     /* world-space end points, finite                                                             */
+  uint8_t  rgb[3], alpha;  /* colour, alpha 0..255                                                                       */
+  uint32_t style;          /* bits 0-3: width in pixels, 1..8; bits 8-9: CRH_ANNOT_ON_TOP / _HIDE / _XRAY; the rest 0     */
+} crh_annot_segment;       /* 32 B */
+typedef struct crh_annot_params {
+  float    depth_bias;     /* relative, >= 0, finite: the scene must be nearer by more than this to occlude; default 0x1p-9 */
+  uint32_t hidden_alpha;   /* 0..255: scales the alpha of occluded XRAY pixels; default 64                                  */
+} crh_annot_params;        /* 8 B */
+/* (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111)  0x1p-9, 64 */
+CRH_API void crh_annot_defaults(crh_annot_params* p);
+/* (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111)  Replace the list; n == 0 or segs == NULL switches the feature
+ * off -- the state of a new context.  params == NULL: the defaults.  Display state: no restart, no work on any stream, allowed before crh_build; the caller's array is
+ * copied.  CRH_E_INVALID with a message: n above CRH_ANNOT_MAX_SEGMENTS; a width of 0 or above 8, mode 3 or any other bit of style set; a NaN / Inf coordinate (or one
+ * beyond 3e38); depth_bias negative or not finite; hidden_alpha above 255.  A refused call leaves the list in force as it was. */
+CRH_API int crh_set_annotations(crh_ctx* ctx, const crh_annot_segment* segs, uint32_t n, const crh_annot_params* params);
+/* (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111)  The list in force (up to `capacity` segments are copied; *n is
+ * the list's length), the parameters (the defaults while off) and whether the feature is on; every pointer may be NULL. */
+CRH_API int crh_get_annotations(crh_ctx* ctx, crh_annot_segment* segs_out, uint32_t capacity, uint32_t* n, crh_annot_params* params_out, int* on);
+/* (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111)  Per pixel, W*H, row 0 = top: the index of the LAST segment that
+ * drew there, or -1; a pixel drawn as x-ray counts as drawn.  All -1 while the feature is off.  Synchronous, on the id buffer's stream; a stale id buffer is computed
+ * first when a segment asks for depth.  Needs a built scene (CRH_E_NOTBUILT).  Touches nothing a read-out could see. */
+CRH_API int crh_read_annotation_ids(crh_ctx* ctx, int32_t* seg_px /* W*H */);
+/* (no counterpart in the reference: ImGuizmo does its own hit test on the handles, ImRaytraceControls.cxx:64)  One pixel of that plane, and the parameter s of the
+ * pixel rule on that segment there (0 at a, 1 at b of the CLIPPED record; 0 when *segment is -1): the hit test for a handle.  Either output may be NULL. */
+CRH_API int crh_pick_annotation(crh_ctx* ctx, uint32_t x, uint32_t y, int32_t* segment, float* s);
+/* (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111)  The projected records as the device computed them for the camera
+ * and frame size in force, 32 B each, n of the list in force (nothing is written while off).  Synchronous.  Needs a built scene (CRH_E_NOTBUILT). */
+CRH_API int crh_read_annotation_records(crh_ctx* ctx, void* records_out /* 32 * n */);
+/* Micro-benchmark (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111): device time of the three kernels a read-out
+ * enqueues for the list in force -- projection, binning, drawing over the frame a read-out issued now would show -- each `repeats` times between two HIP events on the
+ * context's stream, in milliseconds per launch; any output may be NULL.  Synchronous.  Needs a built scene (CRH_E_NOTBUILT) and a list (CRH_E_INVALID).  Touches nothing
+ * a read-out could see. */
+CRH_API int crh_bench_annotations(crh_ctx* ctx, uint32_t repeats, float* project_ms, float* bin_ms, float* draw_ms);
+/* Host-only, no device and no context (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111): THE PROJECTION over n
+ * segments -- the same function the kernel compiles, in a plain loop.  width, height >= 1; the segments checked as crh_set_annotations checks them; else CRH_E_INVALID. */
+CRH_API int crh_annot_project_host(const crh_camera* cam, uint32_t width, uint32_t height, const crh_annot_segment* segs, uint32_t n, void* records_out /* 32 * n */);
+/* Host-only, no device and no context (no counterpart in the reference: ImGui paints over the image, ImRaytraceControls.cxx:64, :93-111): THE PIXEL RULE and the
+ * composite over caller-supplied planes, every segment against every pixel (no bins) -- rays_px 8 floats per pixel in crh_camera_rays' layout, row-major, t_px as
+ * crh_read_ids returns it (both may be NULL when no segment has mode HIDE or XRAY); ldr_inout W*H*3 bytes blended in place, seg_px_out the id plane; either may be NULL.
+ * params == NULL: the defaults.  Checked as crh_set_annotations checks; else CRH_E_INVALID. */
+CRH_API int crh_annot_draw_host(const void* records /* 32 * n */, const crh_annot_segment* segs, uint32_t n, const crh_annot_params* params, const crh_camera* cam,
+                                uint32_t width, uint32_t height, const float* rays_px, const float* t_px, uint8_t* ldr_inout, int32_t* seg_px_out);
+
 /* --- kernel-level entry points (parity tests and micro-benchmarks) ------------------ */
 /* Trace n rays {ox,oy,oz,tmax, dx,dy,dz,tmin-unused} (8 floats each) against the built scene.
  * nearest: out_hit = n x {t, u, v, prim-id-as-int-bits}; prim = -1 on miss, t = tmax.
